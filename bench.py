@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the HIP path-tracer core loop on N MI355X (BASELINE.json metric), one JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--spp S] [--workload bistro|sponza|cornell|principled]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--spp S] [--workload bistro|sponza|cornell|principled] [--dump-outputs DIR]
 
 A "step" is ONE FRAME of the BASELINE configuration: Clear, S = 64 samples per pixel over the whole frame (RenderScene
 iterations 1..S: ray gen -> trace -> shade -> shadow -> [trace -> shade -> shadow] x bounces -> accumulate; the iterations of a
@@ -49,6 +49,10 @@ all per launch:
                node with RAYHIP_BVH_WIDTH=8) + 48 per triangle + 144 per instance, counted by the instrumented product kernel (RAYHIP_FLAG_COUNT_WIDE) on iterations
                of the same workload right after the timed region; next to it the same for the reference's BVH2 walk
                (SURVEY 8d's formula, RAYHIP_FLAG_COUNT_TRAVERSAL) -- what a cache-less machine would have to move
+--dump-outputs DIR: after the timed region, rank 0 writes what the last timed step handed its caller -- the finished frame, raw linear
+RGBA float32 [H, W, 4] -- as DIR/frame_raw.npy.  A frame larger than 64 MB is written as a fixed sample instead: 2^21 pixels drawn
+with seed 0, DIR/frame_raw_sample.npy [n, 4] float32 and their flat indices y * W + x, DIR/frame_raw_sample_index.npy float64.  The
+inputs (scene, camera, PMJ table, iterations 1..S of every step) depend on the arguments alone, so two builds can be compared file by file.
 cpu_baseline: the reference's own AVX2 backend (oracle/_ref, kind "reference"), one persistent pool of worker threads (as
 many as this process may run on: affinity mask and cgroup quota) pulling 32x32 tiles, ALL samples of a tile in one go, on a
 bounded number of spp of the same scene and resolution (rank 0, N=1 only); per-stage split from RendererBase::GetStats.
@@ -94,6 +98,8 @@ WORKLOADS = {
     "cornell": dict(kind="cornell_basic", w=1024, h=1024, label="samples/00_basic Cornell box"),
     "principled": dict(kind="cornell_principled", w=2048, h=2048, label="samples/03_principled Cornell box"),
 }
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 21   # ... and the pixels of the fixed sample of a frame larger than that
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (6.29 TB/s measured copy)
 TILE = 64
 
@@ -109,23 +115,60 @@ def build_scene(scene, wl):
     return scene.triangle_count()
 
 
-def get_scene_blob(name, wl, rank, world, barrier):
-    """rank 0 builds (reference host-side SAH BVH + light tree through SceneHIP) and caches; the others read."""
+def reference_scene_library():
+    """Which library carries the reference's host-side scene code (SAH BVH, light tree, PMJ table) on this tree: the drop-in's
+    (oracle/_ref/hip/libray_hip.so, SceneHIP) or, where only the oracle was built, the oracle's (oracle/_ref/libray_ref.so). Both are
+    made from the reference tree by oracle/Makefile and export through the same ray_amd/host/scene_export.h: their blobs differ only
+    in the unused capacity of the storages (tests/test_hostsim_parity.py renders both)."""
     from ray_amd import api
-    cache_dir = os.environ.get("RAY_AMD_CACHE", "/tmp/ray_amd_cache")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    if os.path.exists(api.HIP_HOST_LIB):
+        return "SceneHIP"
+    if O.have_ref():
+        return "oracle"
+    raise SystemExit(f"bench.py: neither {api.HIP_HOST_LIB} nor {O.REF_LIB} is built -- the scene needs the reference's host scene code "
+                     "(oracle/Makefile, run by __graft_entry__.build() where the reference tree exists)")
+
+
+def export_reference_scene(wl, library):
+    """(blob, unique triangles, triangles in the tree, BVH2 nodes) of workload `wl`, built by `library` (reference_scene_library())"""
+    from ray_amd import api
+    if library == "SceneHIP":
+        s = api.CreateSceneHIP(use_tex_compression=wl.get("compressed", False))
+        ntris = build_scene(s, wl)
+        return api.export_scene_blob(s), ntris, s.triangle_count(), s.node_count()
+    import oracle_lib as O
+    r = O.create_renderer(wl["w"], wl["h"], "REF", use_tex_compression=wl.get("compressed", False))
+    s = r.CreateScene()
+    ntris = build_scene(s, wl)
+    return O.export_scene(s), ntris, s.triangle_count(), s.node_count()
+
+
+def reference_pmj_table(library):
+    from ray_amd import api
+    if library == "SceneHIP":
+        return api.pmj_table()
+    import oracle_lib as O
+    return O.pmj_table()
+
+
+def get_scene_blob(name, wl, rank, world, barrier, library):
+    """rank 0 builds (reference host-side SAH BVH + light tree through `library`) and caches; the others read."""
+    # (default: per user -- a directory another user left in the shared temporary directory may be neither writable nor this tree's)
+    import tempfile
+    cache_dir = os.environ.get("RAY_AMD_CACHE", os.path.join(tempfile.gettempdir(), f"ray_amd_cache_{os.getuid()}"))
     os.makedirs(cache_dir, exist_ok=True)
     path = os.path.join(cache_dir, f"{name}_{wl.get('detail', 0)}{'_decoded' if os.environ.get('RAY_HIP_DECODE_BC') == '1' else ''}.rayscene")
     meta = path + ".json"
     t0 = time.time()
     if rank == 0 and not (os.path.exists(path) and os.path.exists(meta)):
-        s = api.CreateSceneHIP(use_tex_compression=wl.get("compressed", False))
-        ntris = build_scene(s, wl)
-        blob = api.export_scene_blob(s)
+        blob, ntris, bvh_tris, nodes = export_reference_scene(wl, library)
         with open(path + ".tmp", "wb") as f:
             f.write(blob)
         os.replace(path + ".tmp", path)
         with open(meta, "w") as f:
-            json.dump({"tris": int(ntris), "bvh_tris": int(s.triangle_count()), "nodes": int(s.node_count())}, f)
+            json.dump({"tris": int(ntris), "bvh_tris": int(bvh_tris), "nodes": int(nodes)}, f)
     barrier()
     with open(path, "rb") as f:
         blob = f.read()
@@ -236,6 +279,19 @@ def traversal_block(traffic, k2_launches, k3_launches, k2_ms, k3_ms, overlapped,
     return out
 
 
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the finished frame of the last timed step ([H, W, 4] float32), whole or as a fixed, seeded pixel sample"""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame_raw.npy"), frame)
+        return
+    flat = frame.reshape(-1, frame.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=min(DUMP_SAMPLE_PIXELS, flat.shape[0]), replace=False))
+    np.save(os.path.join(out_dir, "frame_raw_sample.npy"), flat[idx])
+    np.save(os.path.join(out_dir, "frame_raw_sample_index.npy"), idx.astype(np.float64))
+
+
 def usable_cpus():
     """hardware threads this process may actually run on: affinity mask, capped by the cgroup CPU quota"""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -328,7 +384,11 @@ def main():
     ap.add_argument("--spp", type=int, default=64)    # samples per pixel of a frame: BASELINE.json quotes the metric at 64
     ap.add_argument("--workload", default=os.environ.get("RAY_AMD_WORKLOAD", "bistro"), choices=sorted(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the last timed step produced to DIR/*.npy (float32, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # The contract is ONE JSON line on stdout.  RCCL prints a version banner with the C library's printf (block-buffered
     # when piped, so it would land after anything Python printed): point file descriptor 1 at stderr for the duration of
@@ -389,10 +449,11 @@ def main():
 
     wl = WORKLOADS[args.workload]
     W, H, K, Wm, SPP = wl["w"], wl["h"], args.steps, args.warmup, max(1, args.spp)
-    blob, info = get_scene_blob(args.workload, wl, rank, world, barrier)
+    scene_library = reference_scene_library()
+    blob, info = get_scene_blob(args.workload, wl, rank, world, barrier, scene_library)
 
     ctx = hip.Context(local_rank)
-    ctx.upload_static(api.pmj_table())
+    ctx.upload_static(reference_pmj_table(scene_library))
     ctx.resize(W, H)
     cam = ctx.upload_scene_blob(blob)
     ctx.set_shard(TILE, world, rank)
@@ -491,6 +552,10 @@ def main():
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
+    # what the last timed step computed, before anything below renders into the same frame buffer again
+    last_frame = None
+    if args.dump_outputs and rank == 0:
+        last_frame = host_frame.copy() if dist is None else ctx.readback(hip.BUF_RAW)
     gc.enable()
     del blob
     it = SPP
@@ -622,6 +687,7 @@ def main():
             "stage_us_per_step": {k: v / K for k, v in stages.items() if v},
             "stage_us_per_spp": {k: v / (K * SPP) for k, v in stages.items() if v},
             "scene_build_s": info["build_s"],
+            "scene_built_by": scene_library,
         }
         # RendererBase::stats_t is a partition of the pass (exclusive intervals of the context stream, include/rayhip.h): the stage entries may not
         # add up to more than the step (they did in round 5, when the shadow launch beside K2 was booked with its elapsed time)
@@ -651,6 +717,8 @@ def main():
         else:
             out["cpu_baseline"] = None
         line = json.dumps(out)
+        if last_frame is not None:
+            dump_outputs(args.dump_outputs, last_frame)
     else:
         line = None
     if comm is not None:

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Compile the drop-in FOR REAL: the reference tree with the INTEGRATION.md patch applied, its own sample unchanged.
 
-    python ray_amd/host/dropin/build_dropin.py [REF=/root/reference]
+    python oracle/build_dropin.py [REF=/root/reference]
 
-What it does (everything lands under ray_amd/host/_build/dropin/, which is git-ignored; the scratch copy of the reference
-is also kept off the GPU box by .gpurunignore -- only the linked binary travels):
+What it does (the scratch copy of the reference and the objects go to oracle/_build/dropin/, git-ignored and not needed at run
+time; only the linked binary lands in oracle/_ref/dropin/, next to the other things compiled from the reference tree, and
+travels with it):
   1. copies the reference's library sources (root *.h / *.cpp, internal/, third-party/renderdoc) and samples/00_basic/main.cpp
-     to _build/dropin/Ray/ -- a scratch copy, never committed;
+     to oracle/_build/dropin/Ray/ -- a scratch copy, never committed;
   2. applies the registration patch of INTEGRATION.md section 2, edit by edit, each anchored on the reference text it
      replaces (an anchor that is not found is an error: the patch in the document and the tree have drifted apart):
         RendererBase.h     enum entry eRendererType::HIP, RendererGPU mask
@@ -17,7 +18,7 @@ is also kept off the GPU box by .gpurunignore -- only the linked binary travels)
      and drops in internal/RendererHIP.h (ray_amd/host/RendererHIP.h);
   3. compiles libRay's translation units (Reference backend + scene code; no SIMD / Vulkan / DX), ray_amd/host/RendererHIP.cpp
      from where it lies, and samples/00_basic/main.cpp UNCHANGED, and links them with librayhip.so into
-     _build/dropin/sample_00_basic.
+     oracle/_ref/dropin/sample_00_basic.
 `Ray::CreateRenderer(s, &Ray::g_stdout_log)` in that sample -- default arguments, not a line touched -- then returns the
 HIP renderer on a box with an MI355X and falls through to the Reference renderer without one (constructor throws, the
 factory logs and goes on: Ray.cpp:58-63's convention).  tests/test_gpu_dropin.py runs the binary on the GPU box and compares its
@@ -31,8 +32,9 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.abspath(os.path.join(HERE, "..", "..", ".."))
-OUT = os.path.join(ROOT, "ray_amd", "host", "_build", "dropin")
+ROOT = os.path.abspath(os.path.join(HERE, ".."))
+SCRATCH = os.path.join(ROOT, "oracle", "_build", "dropin")
+OUT = os.path.join(ROOT, "oracle", "_ref", "dropin")
 
 EDITS = {
     "RendererBase.h": [
@@ -107,10 +109,11 @@ def patch_tree(ref: str, tree: str) -> None:
 
 
 def build(ref: str) -> str:
-    tree = os.path.join(OUT, "Ray")
-    obj = os.path.join(OUT, "obj")
+    tree = os.path.join(SCRATCH, "Ray")
+    obj = os.path.join(SCRATCH, "obj")
     patch_tree(ref, tree)
     os.makedirs(obj, exist_ok=True)
+    os.makedirs(OUT, exist_ok=True)
     inc = ["-I" + tree, "-I" + os.path.join(tree, "internal")]
     jobs = []
     for n in INTERNAL:
@@ -130,7 +133,7 @@ def build(ref: str) -> str:
         objs = list(ex.map(cc, jobs))
     exe = os.path.join(OUT, "sample_00_basic")
     csrc_build = os.path.join(ROOT, "ray_amd", "csrc", "_build")
-    subprocess.run(["g++", "-o", exe, *objs, "-L" + csrc_build, "-lrayhip", "-Wl,-rpath,$ORIGIN/../../../csrc/_build", "-lpthread"], check=True)
+    subprocess.run(["g++", "-o", exe, *objs, "-L" + csrc_build, "-lrayhip", "-Wl,-rpath,$ORIGIN/../../../ray_amd/csrc/_build", "-lpthread"], check=True)
     return exe
 
 

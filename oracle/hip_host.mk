@@ -1,17 +1,24 @@
-# ray_amd/host/Makefile -- builds libray_hip.so: the reference's HOST-SIDE scene code + RendererHIP/SceneHIP + the C view.
+# oracle/hip_host.mk -- builds libray_hip.so: the reference's HOST-SIDE scene code + RendererHIP/SceneHIP + the C view.
+#
+#     make -f hip_host.mk REF=<reference tree>        (from oracle/; the default target of ./Makefile runs it)
 #
 # This is the drop-in as a shared library: what you get when RendererHIP.cpp is added to the reference tree with
 # every other backend disabled.  The reference translation units are compiled where they lie under $(REF)
 # (nothing is copied); only the scene-side ones are needed -- no CPU renderer (CoreRef/ShadeRef's Renderer*
 # instantiations) is linked, so this library has no CPU rendering path at all.
-# Links against ../csrc/_build/librayhip.so (the HIP kernels behind the C ABI).
+# Links against ../ray_amd/csrc/_build/librayhip.so (the HIP kernels behind the C ABI).
 #
-# Needs $(REF) (default /root/reference); on a machine without it the prebuilt library is used as is.
+# It compiles reference sources, so it lands next to the oracle in _ref/ (git-ignored, travels with the tree to a machine
+# without the reference): _ref/hip/libray_hip.so.  Objects and generated headers stay in _build/hip/ (not needed at run time).
+# This file builds the product's host side, not the checker: the rule of ./Makefile (nothing under ray_amd/ loads
+# libray_ref.so) is untouched.
 
 REF      ?= /root/reference
-OUT      := _build
-GEN      := $(OUT)/gen
-OBJ      := $(OUT)/obj
+OUT      := _ref/hip
+TMP      := _build/hip
+GEN      := $(TMP)/gen
+OBJ      := $(TMP)/obj
+HOST     := ../ray_amd/host
 CXX      ?= g++
 CXXFLAGS := -O3 -DNDEBUG -std=c++17 -msse2 -mno-avx -fno-strict-aliasing -fPIC -w \
             -I$(GEN) -I$(GEN)/internal -I$(REF) -I$(REF)/internal
@@ -32,9 +39,9 @@ FLAGS_internal_RadCacheRef := -ffunction-sections -fdata-sections -fvisibility=h
 .PHONY: all clean
 all: $(OUT)/libray_hip.so
 
-$(GEN)/.stamp: ../../tools/gen_ref_blobs.py
-	@mkdir -p $(GEN) $(OBJ)
-	python3 ../../tools/gen_ref_blobs.py $(REF) $(GEN)
+$(GEN)/.stamp: ../tools/gen_ref_blobs.py
+	@mkdir -p $(GEN) $(OBJ) $(OUT)
+	python3 ../tools/gen_ref_blobs.py $(REF) $(GEN)
 	@touch $@
 
 $(OBJ)/internal_%.o: $(REF)/internal/%.cpp $(GEN)/.stamp
@@ -43,13 +50,19 @@ $(OBJ)/internal_%.o: $(REF)/internal/%.cpp $(GEN)/.stamp
 $(OBJ)/simd_detect.o: $(REF)/internal/simd/detect.cpp $(GEN)/.stamp
 	$(CXX) $(CXXFLAGS) -mxsave -c $< -o $@
 
-$(OBJ)/RendererHIP.o: RendererHIP.cpp RendererHIP.h scene_export.h ../../include/rayhip.h $(GEN)/.stamp
-	$(CXX) $(CXXFLAGS) -I. -c RendererHIP.cpp -o $@
-$(OBJ)/ray_capi.o: ray_capi.cpp ray_capi.h RendererHIP.h $(GEN)/.stamp
-	$(CXX) $(CXXFLAGS) -I. -DRAY_CAPI_WITH_HIP -c ray_capi.cpp -o $@
+$(OBJ)/RendererHIP.o: $(HOST)/RendererHIP.cpp $(HOST)/RendererHIP.h $(HOST)/scene_export.h ../include/rayhip.h $(GEN)/.stamp
+	$(CXX) $(CXXFLAGS) -I$(HOST) -c $(HOST)/RendererHIP.cpp -o $@
+$(OBJ)/ray_capi.o: $(HOST)/ray_capi.cpp $(HOST)/ray_capi.h $(HOST)/RendererHIP.h $(GEN)/.stamp
+	$(CXX) $(CXXFLAGS) -I$(HOST) -DRAY_CAPI_WITH_HIP -c $(HOST)/ray_capi.cpp -o $@
 
-$(OUT)/libray_hip.so: $(OBJS) $(OBJ)/RendererHIP.o $(OBJ)/ray_capi.o
-	$(CXX) -shared -Wl,--gc-sections -o $@ $^ -L../csrc/_build -lrayhip -Wl,-rpath,'$$ORIGIN/../../csrc/_build' -lpthread
+# librayhip.so, linked against below: built by __graft_entry__.build() -- or here, when this recipe runs on a checkout where
+# build() has not (the kernels need only hipcc, not the reference tree)
+KERNELS := ../ray_amd/csrc/_build/librayhip.so
+$(KERNELS):
+	cd .. && python3 -c 'import __graft_entry__ as g; g.build_kernels()'
+
+$(OUT)/libray_hip.so: $(OBJS) $(OBJ)/RendererHIP.o $(OBJ)/ray_capi.o | $(KERNELS)
+	$(CXX) -shared -Wl,--gc-sections -o $@ $^ -L../ray_amd/csrc/_build -lrayhip -Wl,-rpath,'$$ORIGIN/../../../ray_amd/csrc/_build' -lpthread
 
 clean:
-	rm -rf $(OUT)
+	rm -rf $(OUT) $(TMP)

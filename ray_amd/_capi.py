@@ -1,7 +1,7 @@
 """ctypes declarations for ray_amd/host/ray_capi.h (the C view of sergcpp/Ray's public API).
 
 The same declarations serve two libraries built from ray_capi.cpp:
-  * ray_amd/host/_build/libray_hip.so  -- reference host-side scene code + RendererHIP/SceneHIP (the product)
+  * oracle/_ref/hip/libray_hip.so      -- reference host-side scene code + RendererHIP/SceneHIP (the product)
   * oracle/_ref/libray_ref.so          -- the reference's own CPU backends (test oracle; tests only)
 """
 import ctypes as C

@@ -29,7 +29,7 @@ import numpy as np
 from . import _capi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-HIP_HOST_LIB = os.path.join(_HERE, "host", "_build", "libray_hip.so")
+HIP_HOST_LIB = os.path.join(os.path.dirname(_HERE), "oracle", "_ref", "hip", "libray_hip.so")
 
 
 class eShadingNode(IntEnum):  # SceneBase.h:46

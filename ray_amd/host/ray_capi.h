@@ -9,7 +9,7 @@
  *
  * Two libraries are built from this file:
  *   oracle/_ref/libray_ref.so          reference CPU backends only               (test oracle / CPU baseline)
- *   ray_amd/host/_build/libray_hip.so  reference host-side scene code + RendererHIP/SceneHIP (the drop-in)
+ *   oracle/_ref/hip/libray_hip.so      reference host-side scene code + RendererHIP/SceneHIP (the drop-in)
  */
 #ifndef RAY_CAPI_H
 #define RAY_CAPI_H

@@ -772,7 +772,7 @@ def atrium(scene, detail: float = 1.0, cam_overrides=None, textured: bool = Fals
 
 
 # ---- the Bistro-class street on the reference's own asset mesh (SURVEY.md section 8d input 4) --------
-ASSET_MESHES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "assets", "_ref", "meshes.npz")
+ASSET_MESHES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "assets", "meshes.npz")
 
 
 def have_asset_meshes() -> bool:

@@ -1,8 +1,8 @@
 """Stages the reference's own test assets for tests/test_material_matrix.py -- the mat_test meshes and those textures of its material tests
-that the checkout has -- into tests/assets/_ref/ (git-ignored: nothing of it enters the history; NOT gpurun-ignored: it travels to the GPU box
-like oracle/_ref, because /root/reference does not exist there).
+that the checkout has -- into oracle/_ref/assets/ (git-ignored: nothing of it enters the history; it travels with the tree like everything else
+under oracle/_ref, because the reference tree does not exist on a GPU machine).
 
-    python tests/golden/stage_ref_assets.py            # needs /root/reference; __graft_entry__.build() runs it when that exists
+    python tests/golden/stage_ref_assets.py [REF=/root/reference]    # needs the reference tree; oracle/Makefile runs it
 
 Everything is DATA, parsed here once and stored as the arrays the tests hand to the API, in compressed .npz containers (smaller to ship, and
 nothing to parse on the GPU box): meshes (tests/test_data/meshes/mat_test/*.bin, layout of tests/utils.cpp:72-114) -> meshes.npz with
@@ -16,9 +16,9 @@ import sys
 
 import numpy as np
 
-REF = "/root/reference/tests/test_data"
+REF = os.path.join(sys.argv[1] if len(sys.argv) > 1 else "/root/reference", "tests", "test_data")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-OUT = os.path.join(ROOT, "tests", "assets", "_ref")
+OUT = os.path.join(ROOT, "oracle", "_ref", "assets")
 MATRIX = os.path.join(ROOT, "tests", "golden", "material_matrix.json")
 
 
@@ -57,7 +57,7 @@ def decode_tga(path):
 
 def main():
     if not os.path.isdir(REF):
-        sys.exit("needs /root/reference (this container); on the GPU box the staged files arrive with the snapshot")
+        sys.exit(f"needs the reference tree ({REF} is missing); on a GPU machine the staged files arrive with oracle/_ref")
     os.makedirs(os.path.join(OUT, "textures"), exist_ok=True)
     staged = []
     meshes = {}
@@ -94,6 +94,11 @@ def main():
             if not os.path.exists(dst):
                 np.savez_compressed(dst, rgb=decode_tga(src))
         staged.append("textures/" + name)
+    # and a fresh extraction of the matrix, for tests/test_material_matrix.py to hold the committed one against
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import make_material_matrix
+    with open(os.path.join(OUT, "material_matrix.json"), "w") as f:
+        json.dump({"tests": make_material_matrix.parse_all(os.path.join(os.path.dirname(REF), "test_shading.cpp"))}, f)
     print(f"staged {len(staged)} files under {OUT}; absent from the checkout (procedural stand-ins in the tests): {absent}")
 
 

@@ -11,8 +11,8 @@ What cannot be the reference's here, and what stands in for it (every substituti
     room / a floor with blocks of the same material groups;
   * 10 of the 23 texture files are absent: a procedural map of the same role (albedo / roughness / metallic / normal) takes their place;
   * `studio_small_03_2k.hdr` is absent: ray_amd.scenes.rgbe_sky.
-The meshes and the textures that ARE in the checkout are staged by tests/golden/stage_ref_assets.py into tests/assets/_ref/ (git-ignored, it
-travels to the GPU box like oracle/_ref): /root/reference does not exist there."""
+The meshes and the textures that ARE in the checkout are staged by tests/golden/stage_ref_assets.py into oracle/_ref/assets/ (git-ignored, it
+travels to a GPU machine with the rest of oracle/_ref): the reference tree does not exist there."""
 import json
 import os
 
@@ -22,7 +22,7 @@ from ray_amd import api, scenes
 from ray_amd.api import PrincipledMat, ShadingNode, eShadingNode, eTextureFormat
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STAGED = os.path.join(ROOT, "tests", "assets", "_ref")
+STAGED = os.path.join(ROOT, "oracle", "_ref", "assets")
 MATRIX = os.path.join(ROOT, "tests", "golden", "material_matrix.json")
 
 VIEW_TRANSFORM = {"Standard": 0, "AgX": 1, "Filmic_HighContrast": 8}  # Types.h:70-82

@@ -1,4 +1,4 @@
-"""The drop-in compiled for real (ray_amd/host/dropin/build_dropin.py): the reference tree with the INTEGRATION.md registration
+"""The drop-in compiled for real (oracle/build_dropin.py): the reference tree with the INTEGRATION.md registration
 patch applied and its own samples/00_basic/main.cpp, unchanged, linked against librayhip.so.  Here (no GPU): the patch must
 apply to the reference as it is -- every edit anchored on the text it replaces -- and the built sample must do what the
 factory convention says on a box without a device: try HIP, log the failure, fall back to the Reference renderer."""
@@ -10,8 +10,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.environ.get("RAY_REFERENCE_DIR", "/root/reference")
-EXE = os.path.join(ROOT, "ray_amd", "host", "_build", "dropin", "sample_00_basic")
-sys.path.insert(0, os.path.join(ROOT, "ray_amd", "host", "dropin"))
+EXE = os.path.join(ROOT, "oracle", "_ref", "dropin", "sample_00_basic")
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "internal")), reason="needs the reference tree")

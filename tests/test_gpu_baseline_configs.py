@@ -40,7 +40,7 @@ def _need_oracle():
         pytest.fail("oracle/_ref/libray_ref.so is missing on the GPU box (it is built by __graft_entry__.build() and ships "
                     "with the snapshot)")
     if not os.path.exists(api.HIP_HOST_LIB):
-        pytest.fail("ray_amd/host/_build/libray_hip.so is missing (SceneHIP)")
+        pytest.fail(f"{api.HIP_HOST_LIB} is missing (SceneHIP)")
 
 
 class Workload:
@@ -108,7 +108,7 @@ def test_asset_street_1080p_against_renderer_ref(name):
     geometry) along a street, baked into one mesh / as 38 mesh instances under a top-level tree -- at 1920 x 1080: iteration 1, then the
     stated 64 spp in one 64-layer pass against RendererRef continued to 64 iterations"""
     if not scenes.have_asset_meshes():
-        pytest.fail("tests/assets/_ref/meshes.npz is missing on the GPU box (staged by __graft_entry__.build(), ships with the snapshot)")
+        pytest.fail(f"{scenes.ASSET_MESHES} is missing (staged by __graft_entry__.build() where the reference tree exists; travels with oracle/_ref)")
     wk = Workload(name)
     wk.ctx.render(1)
     _check(wk.ctx.readback(hip.BUF_RAW), wk.ref_frame(1), util.MIN_PSNR_1SPP, f"{name} 1080p 1 spp")

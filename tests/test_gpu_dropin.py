@@ -1,5 +1,5 @@
 """The drop-in on the device: the reference's own samples/00_basic/main.cpp -- not a line changed -- built against the
-reference tree with the INTEGRATION.md patch applied (ray_amd/host/dropin/build_dropin.py, at build time, where the reference
+reference tree with the INTEGRATION.md patch applied (oracle/build_dropin.py, at build time, where the reference
 tree exists; the binary ships to the GPU box).  `Ray::CreateRenderer(s, &Ray::g_stdout_log)` with its default arguments must
 hand back the HIP renderer, and the TGA the sample writes must be the picture the ctypes path (ray_amd/api.py over the same
 RendererHIP) renders for the same scene: 256 x 256, 64 iterations, tonemapped, 8 bits per channel."""
@@ -14,7 +14,7 @@ from ray_amd import api, hip, scenes
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "ray_amd", "host", "_build", "dropin", "sample_00_basic")
+EXE = os.path.join(ROOT, "oracle", "_ref", "dropin", "sample_00_basic")
 
 
 def _read_tga(path):
@@ -30,7 +30,7 @@ def _read_tga(path):
 def test_the_reference_sample_runs_on_the_hip_renderer(tmp_path):
     assert hip.Library().device_count() > 0, "no HIP device: the product has no CPU path"
     if not os.path.exists(EXE):
-        pytest.fail("ray_amd/host/_build/dropin/sample_00_basic is missing (built by __graft_entry__.build() where the reference tree exists)")
+        pytest.fail("oracle/_ref/dropin/sample_00_basic is missing (built by __graft_entry__.build() where the reference tree exists)")
     r = subprocess.run([EXE], cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
     print(r.stdout[:1500])
     assert r.returncode == 0, r.stderr[-2000:]

@@ -19,7 +19,7 @@ def _need_host_lib():
     if hip.Library().device_count() <= 0:
         pytest.fail("no HIP device: the product has no CPU path")
     if not os.path.exists(api.HIP_HOST_LIB):
-        pytest.fail("ray_amd/host/_build/libray_hip.so is missing (RendererHIP)")
+        pytest.fail(f"{api.HIP_HOST_LIB} is missing (RendererHIP)")
 
 
 def _images(r):

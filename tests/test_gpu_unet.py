@@ -93,7 +93,7 @@ def test_renderer_hip_unet_through_the_ray_api(f32, monkeypatch):
     keeps the exact form."""
     import os
     if not os.path.exists(api.HIP_HOST_LIB):
-        pytest.fail("ray_amd/host/_build/libray_hip.so is missing")
+        pytest.fail(f"{api.HIP_HOST_LIB} is missing")
     if f32:
         monkeypatch.setenv("RAY_HIP_UNET_F32", "1")
     w, h, spp = 96, 64, 4

@@ -389,7 +389,7 @@ def test_asset_street_against_live_reference(lib, instanced, wide, monkeypatch):
     from ray_amd import scenes
 
     if not scenes.have_asset_meshes():
-        pytest.skip("tests/assets/_ref/meshes.npz not staged (needs the reference tree: tests/golden/stage_ref_assets.py)")
+        pytest.skip("oracle/_ref/assets/meshes.npz not staged (needs the reference tree: tests/golden/stage_ref_assets.py)")
     monkeypatch.setenv("HOSTSIM_BVH4", wide)
     monkeypatch.setenv("HOSTSIM_BVH8", "0")
     monkeypatch.setenv("HOSTSIM_REFINE", "0")
@@ -619,3 +619,30 @@ def test_wide_bvh_is_bit_exact(lib, name, width, monkeypatch):
     for it in range(2, 9):
         ctx.render(it)
     assert np.array_equal(ctx.readback(hip.BUF_RAW), g["raw_spp8"])
+
+
+@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("workload", ["cornell", "principled", "sponza"])
+def test_bench_scene_is_the_same_from_either_reference_library(lib, workload):
+    """bench.py builds its scene with the drop-in's host library (SceneHIP) or, on a tree where only the oracle was built, with the
+    oracle's: same reference scene code, same exporter.  The blobs may differ only in the unused capacity of the storages; the host build of
+    the kernels renders the same frame from both, bit for bit (at a reduced size: the sponza-class atrium is 0.3 M triangles)"""
+    import os
+    import sys
+    from ray_amd import api
+    if not os.path.exists(api.HIP_HOST_LIB):
+        pytest.skip("libray_hip.so not built (needs the reference tree at build time)")
+    sys.path.insert(0, util.ROOT)
+    import bench
+    wl = bench.WORKLOADS[workload]
+    a, *ca = bench.export_reference_scene(wl, "SceneHIP")
+    b, *cb = bench.export_reference_scene(wl, "oracle")
+    assert len(a) == len(b) and ca == cb
+    assert np.array_equal(bench.reference_pmj_table("SceneHIP"), bench.reference_pmj_table("oracle"))
+    w, h = 96, 54
+    frames = []
+    for blob in (a, b):
+        ctx = O.hostsim_context(w, h, blob)
+        frames.append(util.render_frames(ctx, 2))
+    assert np.array_equal(frames[0], frames[1])
+    assert float(frames[0].sum()) > 0.0

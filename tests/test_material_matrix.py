@@ -7,13 +7,12 @@ reproduced in this checkout (env.bin and most textures are absent)
 counts -- is extracted mechanically (tests/golden/make_material_matrix.py -> material_matrix.json) and every entry is rendered on the reference's
 mat_test meshes by the live oracle and by this backend (tests/ref_material_scene.py):
 
-  * CPU (`-m "not gpu"`): the committed matrix equals a fresh extraction (when /root/reference is there), and a cross-section of it is BIT-EQUAL
+  * CPU (`-m "not gpu"`): the committed matrix equals the fresh extraction build() staged (where the reference tree was), and a cross-section of it is BIT-EQUAL
     between the host build of the kernel sources and RendererRef -- raw, tonemapped, base colour and depth-normals (tools/material_matrix.py host
     runs all of them: profiles/r05/material_matrix_host.txt);
   * GPU (`-m gpu`): all of them through the C ABI within the stated tolerance of the oracle (tests/util.py)."""
+import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -35,10 +34,7 @@ CPU_SECTION = ["oren_mat1", "sheen_mat3", "aniso_mat5", "tint_mat1", "emit_mat0"
 @pytest.fixture(scope="module")
 def assets():
     if not M.have_assets():
-        if os.path.isdir("/root/reference/tests/test_data"):
-            subprocess.run([sys.executable, os.path.join(util.GOLDEN, "stage_ref_assets.py")], check=True, stdout=subprocess.DEVNULL)
-        else:
-            pytest.skip("tests/assets/_ref is not staged (tests/golden/stage_ref_assets.py needs /root/reference)")
+        pytest.skip("oracle/_ref/assets is not staged (tests/golden/stage_ref_assets.py, run by __graft_entry__.build() where the reference tree exists)")
     if not O.have_ref():
         pytest.skip("oracle/_ref not built")
 
@@ -46,17 +42,17 @@ def assets():
 def test_the_committed_matrix_is_what_the_reference_says():
     assert len(ENTRIES) == 91 and len(set(NAMES)) == 91  # (ninety of test_shading.cpp + test_aux_channels.cpp)
     assert set(CPU_SECTION) <= set(NAMES)
-    src = "/root/reference/tests/test_shading.cpp"
-    if not os.path.exists(src):
-        pytest.skip("/root/reference is not here: the committed matrix stands")
-    sys.path.insert(0, util.GOLDEN)
-    import make_material_matrix
-    assert make_material_matrix.parse_all(src) == ENTRIES
     # every scene variant of the reference's enum is in it, and every descriptor field is one the API mirror knows
     assert {e["scene"] for e in ENTRIES} == {"Standard", "Standard_NoLight", "Refraction_Plane", "Standard_MeshLights", "Two_Sided", "Standard_Clipped",
                                              "Standard_DOF0", "Standard_DOF1", "Standard_SphereLight", "Standard_InsideLight", "Standard_SpotLight",
                                              "Standard_DirLight", "Standard_SunLight", "Standard_MoonLight", "Standard_HDRLight", "Standard_GlassBall0",
                                              "Standard_GlassBall1", "Ray_Flags"}
+    # the extraction build() made from the reference's test sources (tests/golden/stage_ref_assets.py) is the committed one
+    fresh = os.path.join(M.STAGED, "material_matrix.json")
+    if not os.path.exists(fresh):
+        pytest.skip("oracle/_ref/assets is not staged (the reference tree was not there at build time): the committed matrix stands")
+    with open(fresh) as f:
+        assert json.load(f)["tests"] == ENTRIES
 
 
 @pytest.mark.parametrize("name", CPU_SECTION)
@@ -167,7 +163,7 @@ def test_renderer_hip_as_the_reference_harness_drives_it(assets, gpu_lib, name):
     tests/test_gpu_unet.py)."""
     from ray_amd import api
     if not os.path.exists(api.HIP_HOST_LIB):
-        pytest.fail("ray_amd/host/_build/libray_hip.so is missing")
+        pytest.fail(f"{api.HIP_HOST_LIB} is missing")
     entry = ENTRIES[NAMES.index(name)]
     m, (got, ref) = M.run_entry_through_the_api(entry, 96, 96, spp_cap=8)
     if entry["denoise"] == "UNet":

@@ -78,7 +78,7 @@ def test_scene_hip_bakes_its_sky_on_the_device(gpu_lib):
     import os
     import util
     if not os.path.exists(api.HIP_HOST_LIB):
-        pytest.fail("ray_amd/host/_build/libray_hip.so is missing")
+        pytest.fail(f"{api.HIP_HOST_LIB} is missing")
     w, h, spp = 64, 48, 4
     ref, _ = O.render_ref(scenes.cornell_sky, w, h, spp)
     r = api.CreateRenderer(api.Settings(w, h), "HIP")
