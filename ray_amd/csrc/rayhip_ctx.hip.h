@@ -155,6 +155,7 @@ struct rayhip_ctx {
     RaySoA record_rays = {};
     bool notex_kernels = true; // RAYHIP_NOTEX_KERNELS=0: scenes without textures take the general k_surface_scatter too
     bool pick_lds = true; // RAYHIP_PICK_LDS=0: the light pick reads every row of the light table from memory (shade_kernels.hip)
+    bool surface_park = true; // RAYHIP_SURFACE_PARK=0: k_surface_scatter keeps the ray in registers, not in LDS (shade_kernels.hip)
     uint32_t shade_tag = 0;
     uint32_t next_shade_tag() {
         if (++shade_tag == 0u) { // (2^32 launches later: the plane may hold every old tag -- clear it and start again)
@@ -616,6 +617,9 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
     }
     if (const char *e = getenv("RAYHIP_PICK_LDS")) {
         c->pick_lds = atoi(e) != 0;
+    }
+    if (const char *e = getenv("RAYHIP_SURFACE_PARK")) {
+        c->surface_park = atoi(e) != 0;
     }
     // The persistent ray-refill form of the closest-hit kernel (kernels_closest_refill.hip.h): lanes whose ray is finished fetch the next one
     // instead of idling until the longest walk of their wavefront ends.  RAYHIP_REFILL: 2 = for the secondary

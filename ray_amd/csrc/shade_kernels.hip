@@ -550,14 +550,38 @@ __global__ void __launch_bounds__(LDS_TREE ? PICK_BLOCK_WAVES *WAVE : WAVE, LDS_
 #ifndef RT_FUSED_NOTEX_MIN_WAVES
 #define RT_FUSED_NOTEX_MIN_WAVES 3
 #endif
-template <bool PRIMARY, bool SKY, bool TEX = true>
-__global__ void __launch_bounds__(WAVE, TEX ? RT_FUSED_MIN_WAVES : RT_FUSED_NOTEX_MIN_WAVES) k_surface_scatter(const SceneView sc, const ShadeParams sp, const RaySoA rays_in, const HitSoA hits,
+// PARK (round 7): the ray and the pick wait in a per-lane LDS slot while the stages run, and every stage reads what it needs of them from
+// there at the point of use.  Where the register peak of the kernel sits (pre-allocation pressure of <false, false, false>, 153 VGPRs):
+// 144 live values in the analytic-emitter branch of surface_stage (solid_angle_rect), 136 in the triangle set-up, 137 in principled_lobes
+// of scatter_stage -- at all three the ray's throughput, ior stack, cone, pixel and depth and the pick are held for later and not read.
+// The slot is written once per chunk and fenced (park_fence: the compiler may not forward the stored registers past it), so those values
+// leave the register file; what a stage reads comes back with a ds_read next to its use.  Per-lane arithmetic is untouched: frames are
+// bit-identical with RAYHIP_SURFACE_PARK=0 (tests/test_gpu_surface_park.py).
+// Measured (MI355X, bench.py --steps 20 --warmup 5, profiles/r07): the no-texture variants parked hold 128 VGPRs at 4 waves (was 153 / 155
+// at 3).  The kernel takes 12 % less time, and the headline goes from 719.7 to 743.4 Msamples/s.  They still spill 12 B per lane: a
+// constant pair that only the rare portable_acosf branches reload, and SGPR slots in the preamble.  The textured and sky variants
+// (168 VGPRs) stay unparked: they are not measured parked yet.
+#ifndef RT_FUSED_PARK_MIN_WAVES
+#define RT_FUSED_PARK_MIN_WAVES 4
+#endif
+struct ParkedLane {
+    Ray ray;       // 18 dwords
+    float pick[4]; // the slot of the pick plane (light, 1 / probability, u, tag)
+    float pad;     // 23 dwords per lane: an odd stride, so the 64 lanes' dword reads hit 64 different banks
+};
+constexpr size_t PARK_LDS_BYTES = size_t(WAVE) * sizeof(ParkedLane);
+static_assert(sizeof(ParkedLane) % 8u == 4u && PARK_LDS_BYTES <= 10240u, "odd dword stride; at most 10 KB per one-wave block (16 blocks per CU)");
+__device__ __forceinline__ void park_fence() { asm volatile("" ::: "memory"); }
+template <bool PRIMARY, bool SKY, bool TEX = true, bool PARK = false>
+__global__ void __launch_bounds__(WAVE, PARK ? RT_FUSED_PARK_MIN_WAVES : (TEX ? RT_FUSED_MIN_WAVES : RT_FUSED_NOTEX_MIN_WAVES)) k_surface_scatter(const SceneView sc, const ShadeParams sp, const RaySoA rays_in, const HitSoA hits,
                                                                                const RayQueue in, const float4 *__restrict__ picks, const uint32_t tag,
                                                                                const PointSoA records, const RaySoA record_rays, const RayQueue out_records,
                                                                                const RaySoA rays_out, const RayQueue out_rays,
                                                                                const DeferredSoA deferred_out, const RayQueue out_deferred,
                                                                                const PixelBuffers px, const int img_w, const float mix_factor,
                                                                                const Layering layers, uint32_t *__restrict__ sky_index, const RayQueue out_sky) {
+    __shared__ ParkedLane s_park[PARK ? WAVE : 1];
+    ParkedLane &parked = s_park[PARK ? threadIdx.x : 0u];
     const uint32_t n_live_chunks = in.live_chunks();
     const uint32_t fills = in.fill_counts(); // (the input queue's fill counts, in registers: no scalar load per chunk)
     ChunkWalk walk(n_live_chunks);
@@ -571,21 +595,32 @@ __global__ void __launch_bounds__(WAVE, TEX ? RT_FUSED_MIN_WAVES : RT_FUSED_NOTE
         bool continues = false, defer = false, sky = false, lit = false;
         ShadePoint pt;
         SurfaceOut so;
-        Ray ray;
+        Ray ray_regs;
+        Ray &ray = PARK ? parked.ray : ray_regs;
         ShadeParams spl = sp;
         uint32_t xy = 0;
         float4 pick = mkfloat4(0.0f, 0.0f, 0.0f, 0.0f);
         VertexRandoms ahead = {};
         if (active) {
-            ray = load_ray(rays_in, i, sp.plain_ior == 0u);
+            Ray r = load_ray(rays_in, i, sp.plain_ior == 0u);
             const Hit hit = load_hit(hits, i);
-            pick = picks[i]; // (with the ray, not after the surface stage: one round trip less on the wavefront's critical path)
-            xy = ray.xy; // virtual (layered) pixel: where the pixel writes go
+            const float4 pk = picks[i]; // (with the ray, not after the surface stage: one round trip less on the wavefront's critical path)
+            xy = r.xy; // virtual (layered) pixel: where the pixel writes go
             const uint32_t layer = xy_layer(xy, layers);
             spl = layer_params(sp, layer);
-            ray.xy = xy_real(xy, layers, layer);
-            ahead = vertex_randoms(path_random(sc, spl, ray.xy, ray.depth));
+            r.xy = xy_real(xy, layers, layer);
+            ahead = vertex_randoms(path_random(sc, spl, r.xy, r.depth));
+            if (PARK) {
+                parked.ray = r;
+                parked.pick[0] = pk.x, parked.pick[1] = pk.y, parked.pick[2] = pk.z, parked.pick[3] = pk.w;
+                park_fence();
+            } else {
+                ray = r, pick = pk;
+            }
             continues = surface_stage<true, SKY, TEX>(sc, spl, hit, ray, pt, so, &ahead);
+            if (PARK) {
+                park_fence(); // (the record and the continuation read the slot again)
+            }
             defer = so.deferred_emitter;
             sky = SKY && so.deferred_sky;
             if (PRIMARY) {
@@ -602,13 +637,13 @@ __global__ void __launch_bounds__(WAVE, TEX ? RT_FUSED_MIN_WAVES : RT_FUSED_NOTE
                 res.col = so.radiance;
                 add_secondary_pixel(res, xy, img_w, px.temp);
             }
-            lit = continues && sc.light_cwnodes_count != 0 && float_as_uint(pick.w) == tag;
+            lit = continues && sc.light_cwnodes_count != 0 && float_as_uint(PARK ? parked.pick[3] : pick.w) == tag;
         }
         // what the next-event estimation needs of a lit point, densely in the `nee` queue of its stripe
         const uint32_t r_slot = out_records.alloc(stripe, lit);
         if (lit) {
             store_point(records, r_slot, pt, r_slot); // (its "ray slot" is the record's own: record_rays holds the ray's part)
-            records.light[r_slot] = pick;
+            records.light[r_slot] = PARK ? mkfloat4(parked.pick[0], parked.pick[1], parked.pick[2], parked.pick[3]) : pick;
             record_rays.d_cw[r_slot] = mkfloat4(ray.d.x, ray.d.y, ray.d.z, ray.cone_width);
             record_rays.c_cs[r_slot] = mkfloat4(ray.c.x, ray.c.y, ray.c.z, ray.cone_spread);
             if (sp.plain_ior == 0u) {
@@ -775,19 +810,20 @@ void launch(const ShadeLaunch &a) {
 #define RT_FUSED(...) k_surface_scatter<__VA_ARGS__><<<sized(k_surface_scatter<__VA_ARGS__>, a.expect[EXPECT_RAYS], all), WAVE, 0, s>>>( \
         a.sc, a.sp, a.rays_in, a.hits, a.in, a.picks, a.tag, a.points, a.record_rays, a.nee, a.rays_out, a.out_rays, a.deferred, a.out_deferred, a.px, a.vw, \
         a.mix_factor, a.layers, a.sky_index, a.out_sky)
-        const bool sky_scene = a.sc.sky.desc != nullptr;
+        // the parked form (RAYHIP_SURFACE_PARK, default on) for the variants where it measured faster: see RT_FUSED_PARK_MIN_WAVES
+        const bool sky_scene = a.sc.sky.desc != nullptr, park = a.surface_park;
         if (a.bounce == 0) {
             if (sky_scene) {
                 RT_FUSED(true, true);
             } else if (a.no_textures) {
-                RT_FUSED(true, false, false);
+                park ? RT_FUSED(true, false, false, true) : RT_FUSED(true, false, false);
             } else {
                 RT_FUSED(true, false);
             }
         } else if (sky_scene) {
             RT_FUSED(false, true);
         } else if (a.no_textures) {
-            RT_FUSED(false, false, false);
+            park ? RT_FUSED(false, false, false, true) : RT_FUSED(false, false, false);
         } else {
             RT_FUSED(false, false);
         }

@@ -47,6 +47,7 @@ struct ShadeLaunch {
     // planes + `record_rays` (direction | cone width, throughput | cone spread, ior stack, pixel | depth: the planes of a RaySoA, o_pdf unused)
     bool no_textures = false; // the uploaded scene holds no texture at all: k_surface_scatter without the lookups (shade_point.h: TEX)
     bool pick_lds = true; // k_light_pick_first keeps the top of the light table in LDS (RAYHIP_PICK_LDS=0: every row from memory)
+    bool surface_park = true; // k_surface_scatter parks the ray in LDS across its stages (RAYHIP_SURFACE_PARK=0: the ray stays in registers)
     float4 *picks = nullptr;
     uint32_t tag = 0;
     RaySoA record_rays = {};
