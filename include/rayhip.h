@@ -549,6 +549,26 @@ RAYHIP_API int rayhip_finish_import(rayhip_ctx *ctx, const rayhip_camera *cam);
 
 RAYHIP_API int rayhip_sync(rayhip_ctx *ctx);
 
+/* ---- spatial radiance cache: its storage (reference internal/RadCacheRef.{h,cpp}, RendererCPU.h:1165-1232) ----
+ * A hash grid of 2^22 64-bit voxel keys in buckets of 32, with two voxel arrays (previous frames, this frame) of four u32 each:
+ * radiance sums scaled by 1e4 and a word of sample count (low 20 bits) | idle frames (high 12).  32 MiB of keys + 2 x 64 MiB of
+ * voxels, allocated by rayhip_cache_enable(ctx, 1) and freed by rayhip_cache_enable(ctx, 0); every other rayhip_cache_* /
+ * rayhip_k_cache_* call fails while the cache is off.  The calls run on the context stream and wait for it.
+ * Not built yet: the cache-update pass over the renderer's own rays (the reference's UpdateSpatialCache) and the query of the shade
+ * path inside rayhip_render; until then only the kernel-level hooks below fill and read the cache. */
+RAYHIP_API int rayhip_cache_enable(rayhip_ctx *ctx, int on);
+/* ResolveSpatialCache (RendererCPU.h:1165-1211) at camera `cam` (its origin): previous + this frame per key, adjacent-level top-up
+ * when the camera moved since the last resolve, sample cap, idle-frame count, stale keys dropped and every bucket compacted; the
+ * result becomes the previous frames' voxels, this frame's are cleared and the camera position is kept for the next resolve.  The
+ * device resolves every slot first and compacts after (deterministic; the reference's serial order can differ only in adjacent-level
+ * lookups of a moved camera).  GPU time -> rayhip_get_stage_times, time_cache_resolve_us */
+RAYHIP_API int rayhip_cache_resolve(rayhip_ctx *ctx, const rayhip_camera *cam);
+/* ResetSpatialCache (RendererCPU.h:1214-1232): clears the previous frames' voxels only */
+RAYHIP_API int rayhip_cache_reset(rayhip_ctx *ctx);
+/* the first `count` slots of the key table (keys: u64 each, may be NULL) and of a voxel array (voxels: 4 x u32 each, may be NULL;
+ * which: 0 = previous frames', 1 = this frame's) */
+RAYHIP_API int rayhip_cache_readback(rayhip_ctx *ctx, uint64_t *keys, uint32_t *voxels, int which, uint32_t count);
+
 /* traversal counters accumulated by RAYHIP_FLAG_COUNT_TRAVERSAL renders since the last reset:
  * [0] closest-hit kernel (K2), [1] shadow any-hit kernel (K3) */
 RAYHIP_API int rayhip_get_trav_counters(rayhip_ctx *ctx, rayhip_trav_counters out[2], int reset);
@@ -587,6 +607,34 @@ RAYHIP_API int rayhip_k_intersect_shadow(rayhip_ctx *ctx, const rayhip_camera *c
 RAYHIP_API int rayhip_k_shade(rayhip_ctx *ctx, const rayhip_camera *cam, int bounce, int iteration, const rayhip_ray *rays,
                               const rayhip_hit *hits, int count, float *inout_color, rayhip_ray *out_secondary,
                               int *out_secondary_count, rayhip_shadow_ray *out_shadow, int *out_shadow_count);
+/* Spatial cache kernels on host-supplied inputs (tests / measurements only, like the hooks above).
+ * rayhip_cache_grid == cache_grid_params_t (reference Core.h:496-501; log_base 2, scale 50 are the reference's values).
+ * rayhip_cache_vertex: the inputs of Ref::SpatialCacheUpdate (RadCacheRef.cpp:252-309) for one ray -- the vertex is o + t * d; `n`
+ * its geometric normal; `radiance` what the bounce gathered at the path's pixel (throughput not applied); `c` the throughput of the
+ * ray; `ends` nonzero when the ray left the scene or hit a light (nothing is inserted, the radiance flows back along the path);
+ * `path` the index of the path's state (a downsampled pixel). */
+typedef struct rayhip_cache_grid {
+    float cam_pos_curr[3], cam_pos_prev[3];
+    float log_base, scale, exposure;
+} rayhip_cache_grid; /* 36 B */
+typedef struct rayhip_cache_vertex {
+    float o[3], t;
+    float d[3];
+    uint32_t path;
+    float n[3];
+    uint32_t ends;
+    float radiance[3], _pad0;
+    float c[3], _pad1;
+} rayhip_cache_vertex; /* 80 B */
+/* start a pass of `paths` paths: their propagation state (cache_data_t, RAD_CACHE_PROPAGATION_DEPTH = 4 vertices) is cleared */
+RAYHIP_API int rayhip_k_cache_begin_paths(rayhip_ctx *ctx, int paths);
+/* SpatialCacheUpdate for one bounce of `count` vertices (host array, at most one per path: a call naming a path twice is refused):
+ * insert and accumulate into this frame's voxels.  GPU time of the kernel -> rayhip_get_stage_times, time_cache_update_us */
+RAYHIP_API int rayhip_k_cache_update_vertices(rayhip_ctx *ctx, const rayhip_cache_grid *grid, const rayhip_cache_vertex *verts, int count);
+/* the query of the shade path (ShadeRef.cpp:1380-1389) at `count` points (points: [count][6] = position, normal) against the previous
+ * frames' voxels: out[count][4] = mean radiance / exposure and the sample count, all zero when the voxel is missing or holds fewer
+ * than 8 samples */
+RAYHIP_API int rayhip_k_cache_query(rayhip_ctx *ctx, const rayhip_cache_grid *grid, const float *points, int count, float *out);
 /* Ref::get_scrambled_2d_rand (CoreRef.cpp:1418-1427) for `count` (dim,seed,sample) triples */
 RAYHIP_API int rayhip_k_scrambled_rand(rayhip_ctx *ctx, const uint32_t *dims, const uint32_t *seeds,
                                        const int32_t *samples, int count, float *out_xy);

@@ -19,6 +19,7 @@
 
 #include "../../include/rayhip.h"
 #include "kernels.hip.h" // first: it configures the profiling macros the rt_*.h headers expand
+#include "cache_kernels.hip.h"
 #include "shade_launch.h"
 #include "bvh4_build.h"
 #include "bvh4_build.hip.h"
@@ -41,4 +42,5 @@ using namespace rt;
 #include "rayhip_denoise.hip.h"
 #include "rayhip_frames.hip.h"
 #include "rayhip_hooks.hip.h"
+#include "rayhip_cache.hip.h"
 #include "comm.hip.h"

@@ -124,6 +124,16 @@ struct rayhip_ctx {
     bool have_scene = false;
     Shard shard = {64, 1, 0};
 
+    // spatial radiance cache (rayhip_cache_*, rayhip_cache.hip.h): allocated only while enabled
+    bool cache_on = false;
+    DevBuf cache_entries;        // u64 [cache::ENTRIES_COUNT]
+    DevBuf cache_voxels[2];      // cache::Voxel [cache::ENTRIES_COUNT]: [cache_prev] the previous frames', the other this frame's
+    int cache_prev = 0;
+    float cache_cam_prev[3] = {}; // camera position of the last resolve
+    DevBuf cache_paths;          // path state of the pass in progress (cache::PathPlanes)
+    uint32_t cache_path_count = 0;
+    DevBuf cache_io;             // staging of vertices / query points and results
+
     // frame
     int w = 0, h = 0;
     DevBuf px_temp, px_full, px_half, px_raw, px_final, px_base, px_dn, px_req, px_aux_base, px_aux_dn;
@@ -730,6 +740,9 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
     }
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    for (DevBuf *b : {&c->cache_entries, &c->cache_voxels[0], &c->cache_voxels[1], &c->cache_paths, &c->cache_io}) {
+        b->release();
+    }
     if (c->stream2) {
         (void)hipStreamSynchronize(c->stream2);
         (void)hipStreamDestroy(c->stream2);

@@ -66,6 +66,21 @@ class TravCounters(C.Structure):
                 "max_stack": int(self.max_stack), "nodes4": int(self.nodes4)}
 
 
+class CacheGrid(C.Structure):  # rayhip_cache_grid == Ray::cache_grid_params_t
+    _fields_ = [("cam_pos_curr", C.c_float * 3), ("cam_pos_prev", C.c_float * 3), ("log_base", C.c_float), ("scale", C.c_float),
+                ("exposure", C.c_float)]
+
+    @classmethod
+    def make(cls, cam_pos, exposure=1.0, cam_pos_prev=(0.0, 0.0, 0.0)):
+        return cls((C.c_float * 3)(*cam_pos), (C.c_float * 3)(*cam_pos_prev), 2.0, 50.0, exposure)
+
+
+CACHE_ENTRIES = 1 << 22  # slots of the spatial cache's key table (rt_cache.h)
+# rayhip_cache_vertex: one vertex of a cache-update bounce
+CACHE_VERTEX_DTYPE = np.dtype([("o", "<f4", 3), ("t", "<f4"), ("d", "<f4", 3), ("path", "<u4"), ("n", "<f4", 3), ("ends", "<u4"),
+                               ("radiance", "<f4", 3), ("_pad0", "<f4"), ("c", "<f4", 3), ("_pad1", "<f4")])
+assert CACHE_VERTEX_DTYPE.itemsize == 80
+
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("pdf", "<f4"), ("c", "<f4", 3), ("ior", "<f4", 4),
                       ("cone_width", "<f4"), ("cone_spread", "<f4"), ("xy", "<u4"), ("depth", "<u4")])
 SHADOW_RAY_DTYPE = np.dtype([("o", "<f4", 3), ("depth", "<u4"), ("d", "<f4", 3), ("dist", "<f4"), ("c", "<f4", 3),
@@ -82,6 +97,7 @@ ENTRY_POINTS = (
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
     "unet_init", "denoise_unet", "unet_set_precision", "unet_read_tensor",
     "export_shard_device", "owned_bytes", "export_owned", "import_owned", "finish_import",
+    "cache_enable", "cache_resolve", "cache_reset", "cache_readback", "k_cache_begin_paths", "k_cache_update_vertices", "k_cache_query",
 )
 
 
@@ -160,6 +176,13 @@ class Library:
             f("comm_destroy").restype = None
             f("get_trav_timing").argtypes = [vp, C.POINTER(C.c_double * 2), C.POINTER(C.c_ulonglong * 2), C.c_int]
             f("get_stage_times").argtypes = [vp, C.POINTER(Stats), C.c_int]
+            f("cache_enable").argtypes = [vp, C.c_int]
+            f("cache_resolve").argtypes = [vp, C.POINTER(Camera)]
+            f("cache_reset").argtypes = [vp]
+            f("cache_readback").argtypes = [vp, vp, vp, C.c_int, C.c_uint32]
+            f("k_cache_begin_paths").argtypes = [vp, C.c_int]
+            f("k_cache_update_vertices").argtypes = [vp, C.POINTER(CacheGrid), vp, C.c_int]
+            f("k_cache_query").argtypes = [vp, C.POINTER(CacheGrid), vp, C.c_int, vp]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -331,6 +354,43 @@ class Context:
 
     def finish_import(self, cam: Camera = None):
         self.L.check(self.L.fn("finish_import")(self._ctx, C.byref(cam or self.cam)))
+
+    # spatial radiance cache (rayhip.h: rayhip_cache_*; GPU times in stage_times(): cache_update / cache_resolve)
+    def cache_enable(self, on: bool = True):
+        self.L.check(self.L.fn("cache_enable")(self._ctx, int(bool(on))))
+
+    def cache_resolve(self, cam_pos=None, cam: Camera = None):
+        """ResolveSpatialCache at `cam` (its origin), or at a camera standing at `cam_pos`"""
+        if cam is None:
+            cam = Camera()
+            cam.origin[:] = [float(v) for v in cam_pos]
+        self.L.check(self.L.fn("cache_resolve")(self._ctx, C.byref(cam)))
+
+    def cache_reset(self):
+        self.L.check(self.L.fn("cache_reset")(self._ctx))
+
+    def cache_readback(self, which: int = 0, count: int = CACHE_ENTRIES):
+        """(keys u64 [count], voxels u32 [count][4]) of the first `count` slots; which 0: previous frames' voxels, 1: this frame's"""
+        keys = np.zeros(count, dtype=np.uint64)
+        vox = np.zeros((count, 4), dtype=np.uint32)
+        self.L.check(self.L.fn("cache_readback")(self._ctx, keys.ctypes.data, vox.ctypes.data, which, count))
+        return keys, vox
+
+    # test hooks of the cache kernels (rayhip.h: rayhip_k_cache_*)
+    def k_cache_begin_paths(self, paths: int):
+        self.L.check(self.L.fn("k_cache_begin_paths")(self._ctx, int(paths)))
+
+    def k_cache_update_vertices(self, grid: CacheGrid, verts: np.ndarray):
+        """one bounce of CACHE_VERTEX_DTYPE vertices, at most one per path"""
+        verts = np.ascontiguousarray(verts, dtype=CACHE_VERTEX_DTYPE)
+        self.L.check(self.L.fn("k_cache_update_vertices")(self._ctx, C.byref(grid), verts.ctypes.data, len(verts)))
+
+    def k_cache_query(self, grid: CacheGrid, points: np.ndarray) -> np.ndarray:
+        """points [n][6] (position, normal) -> [n][4] (mean radiance / exposure, samples; zero: no answer)"""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 6)
+        out = np.zeros((len(points), 4), dtype=np.float32)
+        self.L.check(self.L.fn("k_cache_query")(self._ctx, C.byref(grid), points.ctypes.data, len(points), out.ctypes.data))
+        return out
 
     # UNet denoiser (rayhip.h: rayhip_unet_init / rayhip_denoise_unet)
     def unet_init(self, weights: np.ndarray, offsets: np.ndarray, alignment: int = 8):
