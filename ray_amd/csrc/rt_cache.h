@@ -90,7 +90,16 @@ RT_HD uint32_t hash_jenkins32(uint32_t a) {
 RT_HD uint32_t hash64(uint64_t key) { return hash_jenkins32(uint32_t(key & 0xffffffffu)) ^ hash_jenkins32(uint32_t(key >> 32)); }
 
 // ---- grid: Core.h:546,564-566, RadCacheRef.cpp:7-13,245-250 ----------------------------------------
-RT_HD float log_base(float x, float base) { return logf(x) / logf(base); }
+// The device's logf is not glibc's: a few floats below a power of two its quotient can reach the integer and the point lands
+// one level over (108 of the 1023 points 2^k (1 +- m ulp), k in [-6, 24], |m| <= 16).  On the device the logarithms are taken
+// in double and rounded once: that gives glibc's level at all of them (tests/test_spatial_cache_hostsim.py pins the formula).
+RT_HD float log_base(float x, float base) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return float(log(double(x))) / float(log(double(base)));
+#else
+    return logf(x) / logf(base);
+#endif
+}
 RT_HD uint32_t calc_grid_level(f3 p, const GridParams &g) {
     const float distance = length(mk3(g.cam_pos_curr) - p);
     const float l = floorf(log_base(distance, g.log_base) + float(LEVEL_BIAS));
@@ -150,7 +159,8 @@ RT_HD uint64_t get_adjacent_level_hash(uint64_t key, const GridParams &g) {
 // ---- hash map: RadCacheRef.cpp:96-127 --------------------------------------------------------------
 RT_HD uint32_t bucket_base(uint64_t key, uint32_t entries_count) { return ((hash64(key) % entries_count) / BUCKET_SIZE) * BUCKET_SIZE; }
 
-// first free (or equal) slot of the key's bucket, INVALID_ENTRY when the bucket is full of other keys
+// first free (or equal) slot of the key's bucket, INVALID_ENTRY when the bucket is full of other keys (the reference answers slot 0
+// there, so its losing keys' samples pile up in slot 0's voxel; this restatement drops them -- its one departure from the reference)
 RT_HD uint32_t hash_map_insert(uint64_t *entries, uint32_t entries_count, uint64_t key) {
     const uint32_t base = bucket_base(key, entries_count);
     for (uint32_t off = 0; off < BUCKET_SIZE && base < entries_count; ++off) {
