@@ -635,6 +635,27 @@ RAYHIP_API int rayhip_k_cache_update_vertices(rayhip_ctx *ctx, const rayhip_cach
  * frames' voxels: out[count][4] = mean radiance / exposure and the sample count, all zero when the voxel is missing or holds fewer
  * than 8 samples */
 RAYHIP_API int rayhip_k_cache_query(rayhip_ctx *ctx, const rayhip_cache_grid *grid, const float *points, int count, float *out);
+/* The tree builders and the wide node test on host-supplied inputs (tests only, like the hooks above; tests/bvh_build_cases.py).
+ * rayhip_k_lbvh_build: the linear builder (lbvh.h) over `n_prims` boxes (boxes: [n_prims][6] = lo.xyz, hi.xyz) in `n_groups` groups
+ * (groups[p] < n_groups), leaf_max 1..8; on_host != 0 runs the plain host loops (build_host) instead of the device kernels.  Outputs
+ * go to caller buffers: out_nodes (capacity nodes_cap, at most n_prims - 1 + n_groups are needed), out_entries (entries_cap, at most
+ * 2 * n_prims), out_group_root[n_groups], out_bounds[6] (lo.xyz, hi.xyz), out_counts[2] = nodes, entries written.  A capacity that
+ * is too small is an error and nothing is written past it. */
+RAYHIP_API int rayhip_k_lbvh_build(rayhip_ctx *ctx, const float *boxes, const uint32_t *groups, uint32_t n_prims, uint32_t n_groups,
+                                   uint32_t leaf_max, int leaf_is_primitive, int roots_are_nodes, int on_host, rayhip_bvh2_node *out_nodes,
+                                   uint32_t nodes_cap, uint32_t *out_entries, uint32_t entries_cap, uint32_t *out_group_root,
+                                   float *out_bounds, uint32_t *out_counts);
+/* the 4-wide collapse on the device (bvh4_build.hip.h) of the trees below `roots` (distinct node indices; every node must be reached
+ * at most once and every link must stay inside the array: anything else is refused before a kernel runs).  out_wide: 64-byte wide nodes
+ * (rt_bvh4.h), capacity n_nodes; out_roots4[n_roots]: the wide node of each root; *out_count: wide nodes written.
+ * Returns 0, 1 (error) or 2: a child box cannot be quantised (no output) */
+RAYHIP_API int rayhip_k_bvh4_collapse(rayhip_ctx *ctx, const rayhip_bvh2_node *nodes, uint32_t n_nodes, const uint32_t *roots,
+                                      uint32_t n_roots, void *out_wide, uint32_t *out_roots4, uint32_t *out_count);
+/* one visit of a wide node per item: node index (< n_wide), ray origin o[3], direction d[3] (inverted the way the walks do, safe_invert)
+ * and distance t -> out_ref[4] (the node's child words, hit ones first by entry distance), out_n_hit, out_dist[4] */
+RAYHIP_API int rayhip_k_bvh4_test_nodes(rayhip_ctx *ctx, const void *wide, uint32_t n_wide, const uint32_t *node_index, const float *ray_o,
+                                        const float *ray_d, const float *ray_t, uint32_t n_items, uint32_t *out_ref, uint32_t *out_n_hit,
+                                        float *out_dist);
 /* Ref::get_scrambled_2d_rand (CoreRef.cpp:1418-1427) for `count` (dim,seed,sample) triples */
 RAYHIP_API int rayhip_k_scrambled_rand(rayhip_ctx *ctx, const uint32_t *dims, const uint32_t *seeds,
                                        const int32_t *samples, int count, float *out_xy);

@@ -63,7 +63,9 @@ RT_HD bool quantise(const Slot *slots, const int n_slots, rt::Bvh4Node &out) {
         if (need > 0.0f) {
             int ex;
             (void)frexpf(need, &ex); // need = m * 2^ex, m in [0.5, 1)
-            e = ex + 127;            // 2^ex >= need
+            // start at 2^(ex-1) <= need and let the loop below widen: 2^ex is one step too large whenever `need` is (or rounded
+            // to) a power of two, e.g. an extent of exactly 255 * 2^k (tests/bvh_build_cases.py: grid_edge_nodes)
+            e = ex + 126;
             if (e < 1) {
                 e = 1;
             }

@@ -1,6 +1,7 @@
 // lbvh.hip.h -- the linear BVH builder of lbvh.h on the device: one kernel per step, rocPRIM's radix sort and prefix sum
 // between them (sort.h).  Same element functions, same IEEE arithmetic -> the same keys, the same radix tree and the same
-// output arrays as rayhip_lbvh::build_host (tests compare the two).  Included by rayhip.hip.
+// output arrays as rayhip_lbvh::build_host (tests/test_gpu_bvh_builders.py compares the two word for word, up to 2^20 + 3 primitives,
+// and holds both against an independent checker, tests/bvh_build_cases.py).  Included by rayhip.hip.
 //
 // Cost on MI355X, 3.0 M triangles in 486 k groups (leaf refinement of the Bistro-class scene): see DESIGN.md (N1).
 #pragma once

@@ -24,6 +24,7 @@
 #include "bvh4_build.h"
 #include "bvh4_build.hip.h"
 #include "bvh8_build.h"
+#include "bvh_hooks.h"
 #include "bvh_layout.h"
 #include "unet.h"
 #include "lbvh.hip.h"

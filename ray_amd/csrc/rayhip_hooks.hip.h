@@ -300,6 +300,119 @@ int rayhip_k_scrambled_rand(rayhip_ctx *c, const uint32_t *dims, const uint32_t 
     return 0;
 }
 
+// ---- the tree builders and the wide node test on caller-supplied inputs (tests/bvh_build_cases.py) --------------------------
+
+int rayhip_k_lbvh_build(rayhip_ctx *c, const float *boxes, const uint32_t *groups, uint32_t n_prims, uint32_t n_groups, uint32_t leaf_max,
+                        int leaf_is_primitive, int roots_are_nodes, int on_host, rayhip_bvh2_node *out_nodes, uint32_t nodes_cap,
+                        uint32_t *out_entries, uint32_t entries_cap, uint32_t *out_group_root, float *out_bounds, uint32_t *out_counts) {
+    std::string why;
+    if (!rayhip_bvh_hooks::check_lbvh_args(boxes, groups, n_prims, n_groups, leaf_max, why)) {
+        return fail("k_lbvh_build: %s", why.c_str());
+    }
+    const rayhip_lbvh::Input in = rayhip_bvh_hooks::lbvh_input(boxes, groups, n_prims, n_groups, leaf_max, leaf_is_primitive, roots_are_nodes);
+    rayhip_lbvh::Output out;
+    if (on_host) {
+        out = rayhip_lbvh::build_host(in);
+    } else {
+        if (use_device(c)) {
+            return 1;
+        }
+        if (!rayhip_lbvh::build_device(c->stream, in, out, why)) {
+            return fail("k_lbvh_build: %s", why.c_str());
+        }
+    }
+    if (!rayhip_bvh_hooks::copy_lbvh_output(out, out_nodes, nodes_cap, out_entries, entries_cap, out_group_root, out_bounds, out_counts, why)) {
+        return fail("k_lbvh_build: %s", why.c_str());
+    }
+    return 0;
+}
+
+int rayhip_k_bvh4_collapse(rayhip_ctx *c, const rayhip_bvh2_node *nodes, uint32_t n_nodes, const uint32_t *roots, uint32_t n_roots,
+                           void *out_wide, uint32_t *out_roots4, uint32_t *out_count) {
+    if (use_device(c)) {
+        return 1;
+    }
+    *out_count = 0;
+    if (n_roots == 0) {
+        return 0;
+    }
+    std::string why;
+    if (!rayhip_bvh_hooks::check_forest(nodes, n_nodes, roots, n_roots, why)) {
+        return fail("k_bvh4_collapse: %s", why.c_str());
+    }
+    hipStream_t s = c->stream;
+    DevBuf d_nodes, d_wide;
+    if (d_nodes.alloc(size_t(n_nodes) * sizeof(rayhip_bvh2_node)) || d_wide.alloc(size_t(n_nodes) * sizeof(Bvh4Node))) {
+        return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(d_nodes.p, nodes, size_t(n_nodes) * sizeof(rayhip_bvh2_node), hipMemcpyHostToDevice, s));
+    const std::vector<uint32_t> root_list(roots, roots + n_roots);
+    uint32_t n_wide = 0;
+    bool unquantisable = false;
+    if (!rayhip_bvh4::build_device(s, d_nodes.as<rayhip_bvh2_node>(), n_nodes, root_list, d_wide.as<Bvh4Node>(), n_wide, why, &unquantisable)) {
+        d_nodes.release(), d_wide.release();
+        if (unquantisable) {
+            return 2;
+        }
+        return fail("k_bvh4_collapse: %s", why.c_str());
+    }
+    HIP_TRY(hipMemcpyAsync(out_wide, d_wide.p, size_t(n_wide) * sizeof(Bvh4Node), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    d_nodes.release(), d_wide.release();
+    for (uint32_t r = 0; r < n_roots; ++r) {
+        out_roots4[r] = r; // (bvh4_build.hip.h: the wide node of roots[r] is r)
+    }
+    *out_count = n_wide;
+    return 0;
+}
+
+// one thread per item; inv_d derived as the walks derive it
+__global__ void __launch_bounds__(256) k_bvh4_test_nodes(const Bvh4Node *__restrict__ wide, const uint32_t *__restrict__ node_index,
+                                                        const float *__restrict__ ray_o, const float *__restrict__ ray_d,
+                                                        const float *__restrict__ ray_t, const uint32_t n_items, uint32_t *__restrict__ out_ref,
+                                                        uint32_t *__restrict__ out_n_hit, float *__restrict__ out_dist) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_items) {
+        rayhip_bvh_hooks::test_node_item(wide, node_index[i], ray_o + size_t(i) * 3, ray_d + size_t(i) * 3, ray_t[i], out_ref + size_t(i) * 4,
+                                         out_n_hit + i, out_dist + size_t(i) * 4);
+    }
+}
+
+int rayhip_k_bvh4_test_nodes(rayhip_ctx *c, const void *wide, uint32_t n_wide, const uint32_t *node_index, const float *ray_o, const float *ray_d,
+                             const float *ray_t, uint32_t n_items, uint32_t *out_ref, uint32_t *out_n_hit, float *out_dist) {
+    if (use_device(c)) {
+        return 1;
+    }
+    if (n_items == 0) {
+        return 0;
+    }
+    std::string why;
+    if (!rayhip_bvh_hooks::check_items(node_index, n_items, n_wide, why)) {
+        return fail("k_bvh4_test_nodes: %s", why.c_str());
+    }
+    hipStream_t s = c->stream;
+    const size_t n = n_items;
+    DevBuf d_wide, d_idx, d_o, d_d, d_t, d_ref, d_hit, d_dist;
+    if (d_wide.alloc(size_t(n_wide) * sizeof(Bvh4Node)) || d_idx.alloc(n * 4) || d_o.alloc(n * 12) || d_d.alloc(n * 12) || d_t.alloc(n * 4) ||
+        d_ref.alloc(n * 16) || d_hit.alloc(n * 4) || d_dist.alloc(n * 16)) {
+        return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(d_wide.p, wide, size_t(n_wide) * sizeof(Bvh4Node), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_idx.p, node_index, n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_o.p, ray_o, n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_d.p, ray_d, n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_t.p, ray_t, n * 4, hipMemcpyHostToDevice, s));
+    k_bvh4_test_nodes<<<(n_items + 255) / 256, 256, 0, s>>>(d_wide.as<Bvh4Node>(), d_idx.as<uint32_t>(), d_o.as<float>(), d_d.as<float>(),
+                                                            d_t.as<float>(), n_items, d_ref.as<uint32_t>(), d_hit.as<uint32_t>(), d_dist.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_ref, d_ref.p, n * 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_n_hit, d_hit.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_dist, d_dist.p, n * 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    d_wide.release(), d_idx.release(), d_o.release(), d_d.release(), d_t.release(), d_ref.release(), d_hit.release(), d_dist.release();
+    return 0;
+}
+
 #if defined(RT_PROFILE_SHADE) || defined(RT_PROFILE_TRACE)
 // tuning build only (tools/variants.py): cycles per shade-kernel section, see RT_PROF in kernels.hip.h
 __attribute__((visibility("default"))) int rayhip_tuning_read_profile(rayhip_ctx *c, unsigned long long out[32], int reset) {

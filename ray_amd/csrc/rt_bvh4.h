@@ -75,7 +75,8 @@ RT_HD float bvh4_dequant(const uint32_t q, const float scale, const float org) {
 //      room to spare; no relative slack on tmin / tmax afterwards (rounds 1-2 used 2^-22 M_a plus a slack of 2^-21: two fma and two
 //      compares more per child);
 //   * the quantised box contains the child box in REAL arithmetic (bvh4_build.h checks org + q * step in double).
-// Checked by the bit-exact frame / hit tests of the wide walk against the BVH2 walk and the oracle.
+// Checked per node visit against the reference's bbox_test on the exact child boxes (tests/test_bvh_builders_hostsim.py:
+// test_node_visit_contract; on the device tests/test_gpu_bvh_builders.py), and by the bit-exact frame / hit tests of the wide walk.
 RT_HD void bvh4_test_node(const Bvh4Node *nodes4, const uint32_t cur, const f3 ro, const f3 inv_d, const float t, uint32_t ref[4],
                           uint32_t &n_hit, float *out_dist = nullptr) {
     RT_PROF_T(16)

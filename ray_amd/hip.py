@@ -98,6 +98,7 @@ ENTRY_POINTS = (
     "unet_init", "denoise_unet", "unet_set_precision", "unet_read_tensor",
     "export_shard_device", "owned_bytes", "export_owned", "import_owned", "finish_import",
     "cache_enable", "cache_resolve", "cache_reset", "cache_readback", "k_cache_begin_paths", "k_cache_update_vertices", "k_cache_query",
+    "k_lbvh_build", "k_bvh4_collapse", "k_bvh4_test_nodes",
 )
 
 
@@ -183,6 +184,10 @@ class Library:
             f("k_cache_begin_paths").argtypes = [vp, C.c_int]
             f("k_cache_update_vertices").argtypes = [vp, C.POINTER(CacheGrid), vp, C.c_int]
             f("k_cache_query").argtypes = [vp, C.POINTER(CacheGrid), vp, C.c_int, vp]
+            u32 = C.c_uint32
+            f("k_lbvh_build").argtypes = [vp, vp, vp, u32, u32, u32, C.c_int, C.c_int, C.c_int, vp, u32, vp, u32, vp, vp, vp]
+            f("k_bvh4_collapse").argtypes = [vp, vp, u32, vp, u32, vp, vp, vp]
+            f("k_bvh4_test_nodes").argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -391,6 +396,49 @@ class Context:
         out = np.zeros((len(points), 4), dtype=np.float32)
         self.L.check(self.L.fn("k_cache_query")(self._ctx, C.byref(grid), points.ctypes.data, len(points), out.ctypes.data))
         return out
+
+    # test hooks of the tree builders and the wide node test (rayhip.h; the host build of the same calls: tests/bvh_build_cases.py)
+    def k_lbvh_build(self, boxes: np.ndarray, groups: np.ndarray, n_groups: int, leaf_max: int, leaf_is_primitive: bool, roots_are_nodes: bool,
+                     on_host: bool = False):
+        """boxes [n][6] (lo, hi), groups [n] -> dict(nodes [k][16] u32 words, entries, group_root, bounds [6])"""
+        boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 6)
+        groups = np.ascontiguousarray(groups, dtype=np.uint32)
+        n = len(boxes)
+        nodes = np.zeros((max(n - 1, 0) + n_groups + 1, 16), dtype=np.uint32)
+        entries = np.zeros(2 * n + 1, dtype=np.uint32)
+        root = np.zeros(n_groups + 1, dtype=np.uint32)
+        bounds = np.zeros(6, dtype=np.float32)
+        counts = np.zeros(2, dtype=np.uint32)
+        self.L.check(self.L.fn("k_lbvh_build")(self._ctx, boxes.ctypes.data, groups.ctypes.data, n, n_groups, leaf_max, int(leaf_is_primitive),
+                                               int(roots_are_nodes), int(on_host), nodes.ctypes.data, len(nodes) - 1, entries.ctypes.data,
+                                               len(entries) - 1, root.ctypes.data, bounds.ctypes.data, counts.ctypes.data))
+        return {"nodes": nodes[:counts[0]].copy(), "entries": entries[:counts[1]].copy(), "group_root": root[:n_groups].copy(), "bounds": bounds}
+
+    def k_bvh4_collapse(self, nodes: np.ndarray, roots: np.ndarray):
+        """BVH2 nodes [k][16] u32 words, roots -> (wide nodes [m][16] u32 words, the wide node of each root), or None: a box cannot be quantised"""
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 16)
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        wide = np.zeros((len(nodes) + 1, 16), dtype=np.uint32)
+        roots4 = np.zeros(len(roots) + 1, dtype=np.uint32)
+        count = C.c_uint32(0)
+        rc = self.L.fn("k_bvh4_collapse")(self._ctx, nodes.ctypes.data, len(nodes), roots.ctypes.data, len(roots), wide.ctypes.data,
+                                          roots4.ctypes.data, C.addressof(count))
+        if rc == 2:
+            return None
+        self.L.check(rc)
+        return wide[:count.value].copy(), roots4[:len(roots)].copy()
+
+    def k_bvh4_test_nodes(self, wide: np.ndarray, node_index, ray_o, ray_d, ray_t):
+        """one node visit per item -> (ref [n][4], n_hit [n], dist [n][4])"""
+        wide = np.ascontiguousarray(wide, dtype=np.uint32).reshape(-1, 16)
+        node_index = np.ascontiguousarray(node_index, dtype=np.uint32)
+        n = len(node_index)
+        o, d = (np.ascontiguousarray(a, dtype=np.float32).reshape(n, 3) for a in (ray_o, ray_d))
+        t = np.ascontiguousarray(ray_t, dtype=np.float32).reshape(n)
+        ref, n_hit, dist = np.zeros((n, 4), np.uint32), np.zeros(n, np.uint32), np.zeros((n, 4), np.float32)
+        self.L.check(self.L.fn("k_bvh4_test_nodes")(self._ctx, wide.ctypes.data, len(wide), node_index.ctypes.data, o.ctypes.data, d.ctypes.data,
+                                                    t.ctypes.data, n, ref.ctypes.data, n_hit.ctypes.data, dist.ctypes.data))
+        return ref, n_hit, dist
 
     # UNet denoiser (rayhip.h: rayhip_unet_init / rayhip_denoise_unet)
     def unet_init(self, weights: np.ndarray, offsets: np.ndarray, alignment: int = 8):
