@@ -492,7 +492,9 @@ RAYHIP_API int rayhip_denoise_unet(rayhip_ctx *ctx, const rayhip_camera *cam, co
  *      half-precision (matrix) arithmetic (internal/RendererVK.cpp:254-263, 1834-1844; RendererGPU.h:533-545): 12.8 x the matrix rate, half the
  *      tensor traffic; RendererHIP selects it like they do (RAY_HIP_UNET_F32=1 keeps the exact form). */
 RAYHIP_API int rayhip_unet_set_precision(rayhip_ctx *ctx, int half);
-/* test hook: activation tensor `which` (0 .. 14 in the order of unet_filter_tensors_t) incl. its one-pixel border, NHWC */
+/* test hook: activation tensor `which` (0 .. 14 in the order of unet_filter_tensors_t) incl. its one-pixel border, NHWC;
+ * 15: the 16-channel image-inputs tensor of the current precision (HDR-transferred radiance, base colour, 0.5 n + 0.5; nine channels
+ * used) as the last pass 0 or 13 wrote it, incl. its border */
 RAYHIP_API int rayhip_unet_read_tensor(rayhip_ctx *ctx, int which, float *dst, size_t capacity_floats, int out_dims[3]);
 
 /* ---- multi-GPU: the frame exchange behind the C ABI (new, the reference has no multi-GPU mode) ----

@@ -329,30 +329,35 @@ int rayhip_unet_set_precision(rayhip_ctx *c, int half) {
     return 0;
 }
 
-// test hook: one activation tensor (0 .. 14, the order of unet_filter_tensors_t) with its border, NHWC; dims = {rows, columns, channels}
+// test hook: one activation tensor (0 .. 14, the order of unet_filter_tensors_t) with its border, NHWC; dims = {rows, columns, channels}.
+// 15: the renderer's three images as the 16-channel tensor k_image_inputs / k_image_inputs_h wrote (nine channels used), with its border
 int rayhip_unet_read_tensor(rayhip_ctx *c, int which, float *dst, size_t capacity_floats, int out_dims[3]) {
     if (use_device(c)) {
         return 1;
     }
-    if (which < 0 || which > 14 || (c->unet_half ? (c->unet_h_w != c->w || !c->unet_tensor_h[which].p) : (c->unet_w != c->w || !c->unet_tensor[which].p))) {
+    if (which < 0 || which > 15) {
         return fail("rayhip_unet_read_tensor: no such tensor (run rayhip_denoise_unet first)");
     }
-    const int wr = round_up16(c->w), hr = round_up16(c->h);
-    out_dims[0] = hr / UNET_TENSOR_DIV[which] + 2, out_dims[1] = wr / UNET_TENSOR_DIV[which] + 2, out_dims[2] = UNET_TENSOR_CH[which];
+    const DevBuf &src = c->unet_half ? (which == 15 ? c->unet_images_h : c->unet_tensor_h[which]) : (which == 15 ? c->unet_images : c->unet_tensor[which]);
+    if ((c->unet_half ? (c->unet_h_w != c->w || c->unet_h_h != c->h) : (c->unet_w != c->w || c->unet_h != c->h)) || !src.p) {
+        return fail("rayhip_unet_read_tensor: no such tensor (run rayhip_denoise_unet first)");
+    }
+    const int wr = round_up16(c->w), hr = round_up16(c->h), div = which == 15 ? 1 : UNET_TENSOR_DIV[which];
+    out_dims[0] = hr / div + 2, out_dims[1] = wr / div + 2, out_dims[2] = which == 15 ? rt::unet::CHUNK : UNET_TENSOR_CH[which];
     const size_t n = size_t(out_dims[0]) * out_dims[1] * out_dims[2];
     if (n > capacity_floats) {
         return fail("rayhip_unet_read_tensor: %zu floats needed", n);
     }
     if (c->unet_half) { // the f16 form's tensor, widened on the host
         std::vector<_Float16> h(n);
-        HIP_TRY(hipMemcpyAsync(h.data(), c->unet_tensor_h[which].p, n * sizeof(_Float16), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h.data(), src.p, n * sizeof(_Float16), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < n; ++i) {
             dst[i] = float(h[i]);
         }
         return 0;
     }
-    HIP_TRY(hipMemcpyAsync(dst, c->unet_tensor[which].p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dst, src.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

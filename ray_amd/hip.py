@@ -456,6 +456,8 @@ class Context:
         self.L.check(self.L.fn("denoise_unet")(self._ctx, C.byref(cam or self.cam), C.byref(r), pass_index))
 
     def unet_read_tensor(self, which: int) -> np.ndarray:
+        """activation tensor 0 .. 14 of the current precision with its one-pixel border, [rows, columns, channels] (f16 tensors widened);
+        15: the 16-channel image-inputs tensor pass 0 / pass 13 wrote"""
         wr, hr = 16 * ((self.w + 15) // 16), 16 * ((self.h + 15) // 16)
         buf = np.zeros((wr + 2) * (hr + 2) * 112, dtype=np.float32)
         dims = (C.c_int * 3)()
