@@ -151,6 +151,7 @@ struct rayhip_ctx {
     int wide = 0; // the wide BLAS form the kernels walk: 4 (rt_bvh4.h, default), 8 (rt_bvh8.h) or 0 (the reference's BVH2)
     uint32_t tex_table[8] = {}, textures_count = 0, tex_flags = 0;
     struct { uint32_t vertices, vtx_indices, tri_materials, materials; } geometry = {};
+    uint32_t instances_count = 0; // mesh instances on the device (scene_upload and scene_update set it)
     bool adaptive_dirty = false; // a pass ran with variance_threshold != 0 since the last Clear / Resize: required_samples may
                                  // lie below the next iteration, so passes are not batched (rayhip_render_batch)
     int lut_transform = 0, lut_dims = 0;
@@ -165,6 +166,10 @@ struct rayhip_ctx {
     RaySoA record_rays = {};
     bool notex_kernels = true; // RAYHIP_NOTEX_KERNELS=0: scenes without textures take the general k_surface_scatter too
     bool pick_lds = true; // RAYHIP_PICK_LDS=0: the light pick reads every row of the light table from memory (shade_kernels.hip)
+    // RAYHIP_SHADE_LDS_TABLES=0: the shade kernels read the material / instance tables from memory, not from a copy in LDS (shade_kernels.hip);
+    // RAYHIP_SHADE_LDS_MATERIALS_MAX / RAYHIP_SHADE_LDS_INSTANCES_MAX lower the counts up to which a scene takes the LDS form
+    bool shade_lds_tables = true;
+    uint32_t shade_lds_materials_max = 0xffffffffu, shade_lds_instances_max = 0xffffffffu;
     bool surface_park = true; // RAYHIP_SURFACE_PARK=0: k_surface_scatter keeps the ray in registers, not in LDS (shade_kernels.hip)
     uint32_t shade_tag = 0;
     uint32_t next_shade_tag() {
@@ -630,6 +635,15 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
     }
     if (const char *e = getenv("RAYHIP_SURFACE_PARK")) {
         c->surface_park = atoi(e) != 0;
+    }
+    if (const char *e = getenv("RAYHIP_SHADE_LDS_TABLES")) {
+        c->shade_lds_tables = atoi(e) != 0;
+    }
+    if (const char *e = getenv("RAYHIP_SHADE_LDS_MATERIALS_MAX")) {
+        c->shade_lds_materials_max = uint32_t(std::max(0, atoi(e)));
+    }
+    if (const char *e = getenv("RAYHIP_SHADE_LDS_INSTANCES_MAX")) {
+        c->shade_lds_instances_max = uint32_t(std::max(0, atoi(e)));
     }
     // The persistent ray-refill form of the closest-hit kernel (kernels_closest_refill.hip.h): lanes whose ray is finished fetch the next one
     // instead of idling until the longest walk of their wavefront ends.  RAYHIP_REFILL: 2 = for the secondary

@@ -368,6 +368,7 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
             upload(c, c->mesh_instances, mis, size_t(d->mesh_instances_count) * sizeof(rayhip_mesh_instance))) {
             return 1;
         }
+        c->instances_count = d->mesh_instances_count;
         // the walks' triangle table: the reference's 48-byte array as it is; RAYHIP_TRI_PITCH=64 re-pitches it so that every record lies in
         // its own 64-byte sector (half of the 48-byte records straddle two) -- measured neutral (K2 2.14 against 2.12 ms,
         // profiles/r03/experiments/variants_tripitch.txt: the kernel is bound by instruction issue, not by sectors), so it stays an option
@@ -612,6 +613,7 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
         (c->wide && upload(c, c->blas_root4, root4.data(), root4.size() * sizeof(uint32_t)))) {
         return 1;
     }
+    c->instances_count = uint32_t(mis.size());
     HIP_TRY(hipStreamSynchronize(c->stream));
     {
         rayhip_scene_desc with_roots = *d; // triangle lights are placed by their instance's transform only

@@ -36,7 +36,7 @@ RT_HD ShadeResult shade_surface(const SceneView &sc, const ShadeParams &sp, cons
     res.emit_secondary = res.emit_shadow = false;
     ShadePoint pt;
     SurfaceOut so;
-    const bool continues = surface_stage<false>(sc, sp, hit, ray, pt, so);
+    const bool continues = surface_stage<false>(sc, scene_tables(sc), sp, hit, ray, pt, so);
     res.col = so.radiance;
     res.base_color = so.base_color;
     res.depth_normal = so.normal_depth;
@@ -46,7 +46,7 @@ RT_HD ShadeResult shade_surface(const SceneView &sc, const ShadeParams &sp, cons
     }
     const LightPick pick = sc.light_cwnodes_count != 0 ? pick_light(sc, pt.P, light_pick_random(sc, sp, ray.xy, ray.depth)) : no_light_pick();
     Scatter sct;
-    scatter_stage(sc, sp, ray, pt, pick, sct);
+    scatter_stage(sc, scene_tables(sc), sp, ray, pt, pick, sct);
     res.col = mk4(direct_radiance(sp, sct, ray.c), 1.0f);
     res.emit_secondary = sct.has_next, res.emit_shadow = sct.has_shadow;
     new_ray = sct.next, sh_r = sct.shadow;

@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(WAVE, RT_SURFACE_MIN_WAVES) k_surface(const Sc
             const uint32_t layer = xy_layer(xy, layers);
             const ShadeParams spl = layer_params(sp, layer);
             ray.xy = xy_real(xy, layers, layer);
-            continues = surface_stage<true, SKY>(sc, spl, hit, ray, pt, so); // (emitter MIS weights: k_shade_emissive)
+            continues = surface_stage<true, SKY>(sc, scene_tables(sc), spl, hit, ray, pt, so); // (emitter MIS weights: k_shade_emissive)
             defer = so.deferred_emitter;
             sky = SKY && so.deferred_sky;
             if (PRIMARY) {
@@ -344,17 +344,71 @@ __device__ __forceinline__ uint32_t queue_fill(const RayQueue &q) {
 }
 __device__ __forceinline__ bool lit_points_are_sparse(const RayQueue &pts, const RayQueue &nee) { return 2u * queue_fill(nee) < queue_fill(pts); }
 
+// ---- round 8: the material and instance tables in LDS ------------------------------------------------------------------------------------
+// What the stages read of a material (76 bytes, a scene has tens) and of an instance (rows 0-2 of inv_xform, four transform_normal calls)
+// is the same for every lane that hit the same surface and is read field by field: each field is a vector-memory instruction whose 64
+// lane addresses go through the CU's address path for a handful of distinct lines.  LDS_TABLES: a block copies both tables into LDS once,
+// before its chunk loop, and the stages read them there through their table argument (shade_point.h: SceneTables); `pt.material` stays
+// an index into the scene's table, the SceneView is not touched, the per-lane arithmetic is the same -- frames are bit-identical
+// (tests/test_gpu_shade_lds_tables.py).  The caps are what the parked kernel leaves of the 10 KB that keep 16 one-wave blocks on a CU; a
+// scene above either cap takes the kernels without the copy (launch(); RAYHIP_SHADE_LDS_TABLES=0 does the same for every scene).
+// Only rows 0-2 of inv_xform are kept: the kernels that take this form defer the emitter MIS weight (k_shade_emissive), the one reader of
+// `xform` and of the fourth row.
+// Measured (MI355X, bench.py --steps 20 --warmup 5, profiles/r08): before, TA_BUSY_avr / (GRBM_GUI_ACTIVE / 8) of k_surface_scatter was 0.67 for the
+// secondary bounces against 0.73 for the closest-hit kernel next to it -- the address path, not only latency.  With the tables in LDS the kernel
+// issues 18.6 instead of 34.7 vector-memory reads per chunk (LDS instructions 40.7 -> 57.5), takes 11.8 % less time (primary: 9.3 %) at the
+// same 128 VGPRs / 4 waves / 12 B of scratch, and the headline goes from 741.9 to 762.1 Msamples/s (medians of three alternating runs each,
+// spreads 2.6 / 1.9).  The next-event kernel reads 23.9 instead of 30.3 per chunk and takes the same time (36.6 ms): it waits elsewhere.
+// The textured and sky variants and k_surface keep the tables in memory: not measured with the copy.
+constexpr uint32_t LDS_MATERIALS_MAX = 48, LDS_INSTANCES_MAX = 14;
+constexpr uint32_t MATERIAL_WORDS = uint32_t(sizeof(rayhip_material) / 4u), INV_XFORM_WORDS = 12;
+constexpr uint32_t LDS_TABLE_WORDS = LDS_MATERIALS_MAX * MATERIAL_WORDS + LDS_INSTANCES_MAX * INV_XFORM_WORDS;
+constexpr size_t LDS_TABLE_BYTES = size_t(LDS_TABLE_WORDS) * 4u;
+static_assert(sizeof(rayhip_material) % 4u == 0u && alignof(rayhip_material) <= 4u, "the material table is copied and addressed as dwords");
+struct LdsTables {
+    const uint32_t *words; // (LDS) LDS_MATERIALS_MAX materials, then INV_XFORM_WORDS floats per instance
+    __device__ __forceinline__ const rayhip_material &material(const uint32_t i) const { return reinterpret_cast<const rayhip_material *>(words)[i]; }
+    __device__ __forceinline__ const float *inv_xform(const uint32_t i) const {
+        return reinterpret_cast<const float *>(words) + LDS_MATERIALS_MAX * MATERIAL_WORDS + i * INV_XFORM_WORDS;
+    }
+};
+// all threads of the block; the caller has checked n_materials / n_instances against the caps (launch())
+__device__ __forceinline__ void fill_lds_tables(uint32_t *words, const SceneView &sc, const uint32_t n_materials, const uint32_t n_instances) {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(sc.materials);
+    for (uint32_t r = threadIdx.x; r < n_materials * MATERIAL_WORDS; r += blockDim.x) {
+        words[r] = src[r];
+    }
+    for (uint32_t r = threadIdx.x; r < n_instances * INV_XFORM_WORDS; r += blockDim.x) {
+        words[LDS_MATERIALS_MAX * MATERIAL_WORDS + r] = float_as_uint(sc.mesh_instances[r / INV_XFORM_WORDS].inv_xform[r % INV_XFORM_WORDS]);
+    }
+    __syncthreads();
+}
+template <bool LDS_TABLES>
+__device__ __forceinline__ auto stage_tables(const SceneView &sc, const uint32_t *words) {
+    if constexpr (LDS_TABLES) {
+        return LdsTables{words};
+    } else {
+        return scene_tables(sc);
+    }
+}
+
 // INDEXED: `in` is the queue of points that got a light (k_light_pick<true>); its slots name the point slots.
 // MODE: 0 = runs unconditionally; 1 = only if the lit points are sparse (the split form); 2 = only if they are not
-template <bool NEE, bool CONTINUE, bool INDEXED = false, int MODE = 0>
+// LDS_TABLES: the material table from LDS (above)
+template <bool NEE, bool CONTINUE, bool INDEXED = false, int MODE = 0, bool LDS_TABLES = false>
 __global__ void __launch_bounds__(WAVE, (NEE && CONTINUE) ? RT_SCATTER_MIN_WAVES : (NEE ? RT_SCATTER_NEE_MIN_WAVES : RT_SCATTER_CONT_MIN_WAVES)) k_scatter(const SceneView sc, const ShadeParams sp, const RaySoA rays_in,
                                                                        const PointSoA points, const RayQueue in, const RaySoA rays_out,
                                                                        const RayQueue out_rays, const ShadowSoA shadow_out, const RayQueue out_shadow,
                                                                        const PixelBuffers px, const int img_w, const Layering layers,
-                                                                       const RayQueue all_points, const RayQueue lit_points) {
+                                                                       const RayQueue all_points, const RayQueue lit_points, const uint32_t n_materials) {
     if (MODE != 0 && lit_points_are_sparse(all_points, lit_points) != (MODE == 1)) {
         return;
     }
+    __shared__ uint32_t s_tables[LDS_TABLES ? LDS_TABLE_WORDS : 1];
+    if (LDS_TABLES) {
+        fill_lds_tables(s_tables, sc, n_materials, 0u);
+    }
+    const auto tb = stage_tables<LDS_TABLES>(sc, s_tables);
     const uint32_t n_live_chunks = in.live_chunks();
     ChunkWalk walk(n_live_chunks);
     for (uint32_t c; walk.next(c);) {
@@ -386,7 +440,7 @@ __global__ void __launch_bounds__(WAVE, (NEE && CONTINUE) ? RT_SCATTER_MIN_WAVES
             const uint32_t layer = xy_layer(xy, layers);
             const ShadeParams spl = layer_params(sp, layer);
             ray.xy = xy_real(xy, layers, layer);
-            scatter_stage<NEE, CONTINUE>(sc, spl, ray, pt, pick, sct);
+            scatter_stage<NEE, CONTINUE>(sc, tb, spl, ray, pt, pick, sct);
             sct.next.xy = xy, sct.shadow.xy = xy;
             if (NEE) {
                 const f3 col = direct_radiance(spl, sct, ray.c);
@@ -572,16 +626,23 @@ struct ParkedLane {
 constexpr size_t PARK_LDS_BYTES = size_t(WAVE) * sizeof(ParkedLane);
 static_assert(sizeof(ParkedLane) % 8u == 4u && PARK_LDS_BYTES <= 10240u, "odd dword stride; at most 10 KB per one-wave block (16 blocks per CU)");
 __device__ __forceinline__ void park_fence() { asm volatile("" ::: "memory"); }
-template <bool PRIMARY, bool SKY, bool TEX = true, bool PARK = false>
+static_assert(PARK_LDS_BYTES + LDS_TABLE_BYTES <= 10240u, "parked slots + tables: at most 10 KB per one-wave block (16 blocks per CU)");
+template <bool PRIMARY, bool SKY, bool TEX = true, bool PARK = false, bool LDS_TABLES = false>
 __global__ void __launch_bounds__(WAVE, PARK ? RT_FUSED_PARK_MIN_WAVES : (TEX ? RT_FUSED_MIN_WAVES : RT_FUSED_NOTEX_MIN_WAVES)) k_surface_scatter(const SceneView sc, const ShadeParams sp, const RaySoA rays_in, const HitSoA hits,
                                                                                const RayQueue in, const float4 *__restrict__ picks, const uint32_t tag,
                                                                                const PointSoA records, const RaySoA record_rays, const RayQueue out_records,
                                                                                const RaySoA rays_out, const RayQueue out_rays,
                                                                                const DeferredSoA deferred_out, const RayQueue out_deferred,
                                                                                const PixelBuffers px, const int img_w, const float mix_factor,
-                                                                               const Layering layers, uint32_t *__restrict__ sky_index, const RayQueue out_sky) {
+                                                                               const Layering layers, uint32_t *__restrict__ sky_index, const RayQueue out_sky,
+                                                                               const uint32_t n_materials, const uint32_t n_instances) {
     __shared__ ParkedLane s_park[PARK ? WAVE : 1];
+    __shared__ uint32_t s_tables[LDS_TABLES ? LDS_TABLE_WORDS : 1]; // (its own array: the park slots and the tables cannot overlap)
     ParkedLane &parked = s_park[PARK ? threadIdx.x : 0u];
+    if (LDS_TABLES) {
+        fill_lds_tables(s_tables, sc, n_materials, n_instances);
+    }
+    const auto tb = stage_tables<LDS_TABLES>(sc, s_tables);
     const uint32_t n_live_chunks = in.live_chunks();
     const uint32_t fills = in.fill_counts(); // (the input queue's fill counts, in registers: no scalar load per chunk)
     ChunkWalk walk(n_live_chunks);
@@ -617,7 +678,7 @@ __global__ void __launch_bounds__(WAVE, PARK ? RT_FUSED_PARK_MIN_WAVES : (TEX ? 
             } else {
                 ray = r, pick = pk;
             }
-            continues = surface_stage<true, SKY, TEX>(sc, spl, hit, ray, pt, so, &ahead);
+            continues = surface_stage<true, SKY, TEX>(sc, tb, spl, hit, ray, pt, so, &ahead);
             if (PARK) {
                 park_fence(); // (the record and the continuation read the slot again)
             }
@@ -671,7 +732,7 @@ __global__ void __launch_bounds__(WAVE, PARK ? RT_FUSED_PARK_MIN_WAVES : (TEX ? 
         sct.has_next = sct.has_shadow = false;
         if (continues) {
             ray.o = pt.P, ray.pdf = 0.0f; // (what k_scatter hands the stage: neither is read by it)
-            scatter_stage<false, true>(sc, spl, ray, pt, no_light_pick(), sct, &ahead);
+            scatter_stage<false, true>(sc, tb, spl, ray, pt, no_light_pick(), sct, &ahead);
             sct.next.xy = xy;
         }
         const uint32_t n_slot = out_rays.alloc(stripe, sct.has_next);
@@ -809,21 +870,32 @@ void launch(const ShadeLaunch &a) {
         }
 #define RT_FUSED(...) k_surface_scatter<__VA_ARGS__><<<sized(k_surface_scatter<__VA_ARGS__>, a.expect[EXPECT_RAYS], all), WAVE, 0, s>>>( \
         a.sc, a.sp, a.rays_in, a.hits, a.in, a.picks, a.tag, a.points, a.record_rays, a.nee, a.rays_out, a.out_rays, a.deferred, a.out_deferred, a.px, a.vw, \
-        a.mix_factor, a.layers, a.sky_index, a.out_sky)
+        a.mix_factor, a.layers, a.sky_index, a.out_sky, a.n_materials, a.n_instances)
         // the parked form (RAYHIP_SURFACE_PARK, default on) for the variants where it measured faster: see RT_FUSED_PARK_MIN_WAVES
         const bool sky_scene = a.sc.sky.desc != nullptr, park = a.surface_park;
+        // the tables in LDS (RAYHIP_SHADE_LDS_TABLES, default on) where both fit: the no-texture variants and the next-event kernel
+        const bool lds_tables = a.lds_tables && a.n_materials != 0u && a.n_materials <= std::min(a.lds_materials_max, LDS_MATERIALS_MAX) &&
+                                a.n_instances != 0u && a.n_instances <= std::min(a.lds_instances_max, LDS_INSTANCES_MAX);
         if (a.bounce == 0) {
             if (sky_scene) {
                 RT_FUSED(true, true);
             } else if (a.no_textures) {
-                park ? RT_FUSED(true, false, false, true) : RT_FUSED(true, false, false);
+                if (lds_tables) {
+                    park ? RT_FUSED(true, false, false, true, true) : RT_FUSED(true, false, false, false, true);
+                } else {
+                    park ? RT_FUSED(true, false, false, true) : RT_FUSED(true, false, false);
+                }
             } else {
                 RT_FUSED(true, false);
             }
         } else if (sky_scene) {
             RT_FUSED(false, true);
         } else if (a.no_textures) {
-            park ? RT_FUSED(false, false, false, true) : RT_FUSED(false, false, false);
+            if (lds_tables) {
+                park ? RT_FUSED(false, false, false, true, true) : RT_FUSED(false, false, false, false, true);
+            } else {
+                park ? RT_FUSED(false, false, false, true) : RT_FUSED(false, false, false);
+            }
         } else {
             RT_FUSED(false, false);
         }
@@ -833,8 +905,11 @@ void launch(const ShadeLaunch &a) {
         }
         k_shade_emissive<<<sized(k_shade_emissive, a.expect[EXPECT_DEFERRED], 2048), WAVE, 0, s>>>(a.sc, a.sp, a.rays_in, a.hits, a.deferred, a.out_deferred, a.px, a.vw);
         if (lights) { // the records name themselves as their ray slot: the ray's part comes from record_rays
-            k_scatter<true, false><<<sized(k_scatter<true, false>, a.expect[EXPECT_LIT], all), WAVE, 0, s>>>(
-                a.sc, a.sp, a.record_rays, a.points, a.nee, a.rays_out, a.out_rays, a.shadow, a.out_shadow, a.px, a.vw, a.layers, a.pts, a.nee);
+            auto nee = [&](auto kernel) {
+                kernel<<<sized(kernel, a.expect[EXPECT_LIT], all), WAVE, 0, s>>>(
+                    a.sc, a.sp, a.record_rays, a.points, a.nee, a.rays_out, a.out_rays, a.shadow, a.out_shadow, a.px, a.vw, a.layers, a.pts, a.nee, a.n_materials);
+            };
+            (lds_tables && a.no_textures) ? nee(k_scatter<true, false, false, 0, true>) : nee(k_scatter<true, false>);
         }
         return;
     }
@@ -902,7 +977,7 @@ void launch(const ShadeLaunch &a) {
         k_light_pick<false><<<sized(k_light_pick<false>, a.expect[EXPECT_POINTS], all), WAVE, 0, s>>>(a.sc, a.sp, a.rays_in, a.points, a.pts, a.nee, a.layers);
     }
     // stage 3: shadow ray + continuation
-#define RT_SCATTER_ARGS(queue) a.sc, a.sp, a.rays_in, a.points, queue, a.rays_out, a.out_rays, a.shadow, a.out_shadow, a.px, a.vw, a.layers, a.pts, a.nee
+#define RT_SCATTER_ARGS(queue) a.sc, a.sp, a.rays_in, a.points, queue, a.rays_out, a.out_rays, a.shadow, a.out_shadow, a.px, a.vw, a.layers, a.pts, a.nee, a.n_materials
 #define RT_SCATTER(queue, expect, ...) k_scatter<__VA_ARGS__><<<sized(k_scatter<__VA_ARGS__>, expect, all), WAVE, 0, s>>>(RT_SCATTER_ARGS(queue))
     if (nee_compact) {
         // the next-event estimation runs over the points that have a light to sample -- full wavefronts instead of the 11 of 64

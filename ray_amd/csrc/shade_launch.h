@@ -48,6 +48,12 @@ struct ShadeLaunch {
     bool no_textures = false; // the uploaded scene holds no texture at all: k_surface_scatter without the lookups (shade_point.h: TEX)
     bool pick_lds = true; // k_light_pick_first keeps the top of the light table in LDS (RAYHIP_PICK_LDS=0: every row from memory)
     bool surface_park = true; // k_surface_scatter parks the ray in LDS across its stages (RAYHIP_SURFACE_PARK=0: the ray stays in registers)
+    // round 8: k_surface_scatter (no-texture variants) and the next-event kernel read the material / instance tables from a copy in LDS when the
+    // scene's counts (0: unknown -> never) are within the caps: the kernels' own (shade_kernels.hip: LDS_MATERIALS_MAX / LDS_INSTANCES_MAX), lowered
+    // by RAYHIP_SHADE_LDS_MATERIALS_MAX / RAYHIP_SHADE_LDS_INSTANCES_MAX; RAYHIP_SHADE_LDS_TABLES=0: every scene reads them from memory
+    bool lds_tables = true;
+    uint32_t n_materials = 0, n_instances = 0;
+    uint32_t lds_materials_max = 0xffffffffu, lds_instances_max = 0xffffffffu;
     float4 *picks = nullptr;
     uint32_t tag = 0;
     RaySoA record_rays = {};

@@ -396,12 +396,13 @@ RT_HD void principled_continue(const ScatterFrame &fr, const ShadePoint &pt, con
 
 // ---- the scatter stage ------------------------------------------------------------------------------------------------------------------
 // `ray`: the ray that produced the shade point (direction, throughput, ior stack, cone, pixel, depth counters)
-template <bool NEE = true, bool CONTINUE = true>
-RT_HD void scatter_stage(const SceneView &sc, const ShadeParams &sp, const Ray &ray, const ShadePoint &pt, const LightPick &pick, Scatter &out,
+// `tb`: where the material table is read from (shade_point.h: SceneTables)
+template <bool NEE = true, bool CONTINUE = true, class Tables = SceneTables>
+RT_HD void scatter_stage(const SceneView &sc, const Tables &tb, const ShadeParams &sp, const Ray &ray, const ShadePoint &pt, const LightPick &pick, Scatter &out,
                          const VertexRandoms *ahead = nullptr) {
     RT_PROF_SHADE_LANES(0)
     const PassLimits &ps = sp.ps;
-    const rayhip_material &mat = sc.materials[pt.material];
+    const rayhip_material &mat = tb.material(pt.material);
     const PathRandom rnd = path_random(sc, sp, ray.xy, ray.depth);
 
     ScatterFrame fr;

@@ -265,14 +265,27 @@ RT_HD f4 emissive_hit_radiance(const ShadeParams &sp, const float mix_weight, co
     return mk4(clamp_radiance_sum(c, sp.limits[1]), 1.0f);
 }
 
+// ---- where the stages read the material and instance tables -----------------------------------------------------------------------------
+// Both tables are tiny (76 bytes per material, tens of them; a handful of instances), shared by every lane and read field by field:
+// surface_stage and scatter_stage take them through an argument of their own, so that a kernel can serve them from a copy in LDS
+// (shade_kernels.hip: LdsTables) without touching the SceneView -- which is never copied or modified; every other table is read through
+// it as before.  `inv_xform(i)` is rows 0-2 of the instance's world-to-object matrix: all that transform_normal reads.
+struct SceneTables {
+    const rayhip_material *materials;
+    const rayhip_mesh_instance *instances;
+    RT_HD const rayhip_material &material(const uint32_t i) const { return materials[i]; }
+    RT_HD const float *inv_xform(const uint32_t i) const { return instances[i].inv_xform; }
+};
+RT_HD SceneTables scene_tables(const SceneView &sc) { return SceneTables{sc.materials, sc.mesh_instances}; }
+
 // ---- the surface stage -----------------------------------------------------------------------------------------------------------
 // Returns true when `pt` was filled (the path continues through stages 2 and 3), false when the path ends with out.radiance.
 // DEFER_EMITTERS: leave the MIS weight of emitter hits to the caller (see SurfaceOut).
 // SKY: the environment may be the physical sky (false: the test is compiled out -- the device picks the kernel per scene).
 // TEX (round 6): false when the uploaded scene holds NO texture (SceneView::tex_flags / textures_count: decided at upload, exact) -- every texture
 // lookup of the stage is compiled out, which is worth 20 registers to k_surface_scatter (175 -> 153 at its peak).
-template <bool DEFER_EMITTERS, bool SKY = true, bool TEX = true>
-RT_HD bool surface_stage(const SceneView &sc, const ShadeParams &sp, const Hit &hit, const Ray &ray, ShadePoint &pt, SurfaceOut &out,
+template <bool DEFER_EMITTERS, bool SKY = true, bool TEX = true, class Tables = SceneTables>
+RT_HD bool surface_stage(const SceneView &sc, const Tables &tb, const ShadeParams &sp, const Hit &hit, const Ray &ray, ShadePoint &pt, SurfaceOut &out,
                          const VertexRandoms *ahead = nullptr) {
     out.radiance = f4{0.0f, 0.0f, 0.0f, 0.0f};
     out.base_color = f3{0.0f, 0.0f, 0.0f};
@@ -322,7 +335,7 @@ RT_HD bool surface_stage(const SceneView &sc, const ShadeParams &sp, const Hit &
     pt.P = ray.o + hit.t * view;
     pt.backfacing = (hit.prim_index < 0);
     const uint32_t tri = pt.backfacing ? uint32_t(-hit.prim_index - 1) : uint32_t(hit.prim_index);
-    const rayhip_mesh_instance *inst = &sc.mesh_instances[hit.obj_index];
+    const float *inv_xform = tb.inv_xform(uint32_t(hit.obj_index));
     const float4 *rows = sc.tri_verts + size_t(tri) * TRI_VERTS_STRIDE;
     const Corner c1 = load_corner(rows), c2 = load_corner(rows + 2), c3 = load_corner(rows + 4);
     const float4 plane = rows[6];
@@ -336,16 +349,16 @@ RT_HD bool surface_stage(const SceneView &sc, const ShadeParams &sp, const Hit &
     const float twice_area_obj = plane.w;
     f3 Ng = {plane.x, plane.y, plane.z}, N = N_obj;
 
-    const rayhip_material *mat = &sc.materials[sides.front_mi & MATERIAL_INDEX_BITS];
+    uint32_t mat_index = sides.front_mi & MATERIAL_INDEX_BITS;
     if (pt.backfacing) {
         if (sides.back_mi == 0xffff) {
             return false; // single-sided: nothing there from this side (radiance and coverage stay zero)
         }
-        mat = &sc.materials[sides.back_mi & MATERIAL_INDEX_BITS];
+        mat_index = sides.back_mi & MATERIAL_INDEX_BITS;
         Ng = -Ng, N = -N;
     }
-    Ng = safe_normalize(transform_normal(Ng, inst->inv_xform));
-    N = safe_normalize(transform_normal(N, inst->inv_xform));
+    Ng = safe_normalize(transform_normal(Ng, inv_xform));
+    N = safe_normalize(transform_normal(N, inv_xform));
 
     // texture level of detail from the ray-cone footprint: uv area over surface area, times the cone width
     pt.cone_width = ray.cone_width + ray.cone_spread * hit.t;
@@ -358,6 +371,7 @@ RT_HD bool surface_stage(const SceneView &sc, const ShadeParams &sp, const Hit &
     const f2 pick = ahead ? ahead->bsdf_pick : rnd.get(RAND_DIM_BSDF_PICK);
     float mix_u = pick.x;
     pt.mix_weight = 1.0f;
+    const rayhip_material *mat = &tb.material(mat_index);
     while (mat->type == NODE_MIX) {
         float k = mat->tangent_rotation_or_strength;
         if (TEX && mat->textures[BASE_TEXTURE] != 0xffffffff) {
@@ -369,16 +383,17 @@ RT_HD bool surface_stage(const SceneView &sc, const ShadeParams &sp, const Hit &
         const bool additive = (mat->flags & MAT_FLAG_MIX_ADD) != 0;
         if (mix_u > k) {
             pt.mix_weight *= additive ? 1.0f / (1.0f - k) : 1.0f;
-            mat = &sc.materials[mat->textures[MIX_MAT1]];
+            mat_index = mat->textures[MIX_MAT1];
             mix_u = safe_div_pos(mix_u - k, 1.0f - k);
         } else {
             pt.mix_weight *= additive ? 1.0f / k : 1.0f;
-            mat = &sc.materials[mat->textures[MIX_MAT2]];
+            mat_index = mat->textures[MIX_MAT2];
             mix_u = safe_div_pos(mix_u, k);
         }
+        mat = &tb.material(mat_index);
     }
     pt.mix_pick = mix_u;
-    pt.material = uint32_t(mat - sc.materials);
+    pt.material = mat_index;
 
     // ---- normal map, bent back above the horizon of the view direction ----
     if (TEX && mat->textures[NORMALS_TEXTURE] != 0xffffffff) {
@@ -398,8 +413,8 @@ RT_HD bool surface_stage(const SceneView &sc, const ShadeParams &sp, const Hit &
         if (pt.backfacing) {
             Bt = -Bt, Tg = -Tg;
         }
-        Bt = safe_normalize(transform_normal(Bt, inst->inv_xform));
-        Tg = safe_normalize(transform_normal(Tg, inst->inv_xform));
+        Bt = safe_normalize(transform_normal(Bt, inv_xform));
+        Tg = safe_normalize(transform_normal(Tg, inv_xform));
         const f3 smooth = N;
         N = normalize(nm.x * Tg + nm.z * N + nm.y * Bt);
         if (mat->normal_map_strength_unorm != 0xffff) {
@@ -410,9 +425,9 @@ RT_HD bool surface_stage(const SceneView &sc, const ShadeParams &sp, const Hit &
 
     // ---- anisotropy frame: the radial direction around the object's Y axis, optionally rotated about N ----
     const f3 P_obj = c1.p * w1 + c2.p * hit.u + c3.p * hit.v;
-    f3 radial = transform_normal(f3{-P_obj.z, 0.0f, P_obj.x}, inst->inv_xform);
+    f3 radial = transform_normal(f3{-P_obj.z, 0.0f, P_obj.x}, inv_xform);
     if (length2(cross(radial, N)) == 0.0f) {
-        radial = transform_normal(P_obj, inst->inv_xform);
+        radial = transform_normal(P_obj, inv_xform);
     }
     if (mat->tangent_rotation_or_strength != 0.0f) {
         radial = rotate_about_axis(radial, N, mat->tangent_rotation_or_strength);
@@ -470,7 +485,7 @@ RT_HD bool surface_stage(const SceneView &sc, const ShadeParams &sp, const Hit &
             out.emitter_mix_weight = pt.mix_weight;
             mis = 0.0f;
         } else {
-            mis = emissive_hit_mis_weight(sc, ray.o, view, pt.P, hit.t, ray.pdf, tri, inst);
+            mis = emissive_hit_mis_weight(sc, ray.o, view, pt.P, hit.t, ray.pdf, tri, &sc.mesh_instances[hit.obj_index]);
         }
     }
     out.radiance = emissive_hit_radiance(sp, pt.mix_weight, mis, mat->tangent_rotation_or_strength, pt.base, ray.c);
