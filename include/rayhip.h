@@ -406,6 +406,27 @@ RAYHIP_API int rayhip_scene_upload_blob(rayhip_ctx *ctx, const void *blob, size_
 /* rayhip_scene_update_instances from a serialised scene (same return values; the filter table in the blob is ignored) */
 RAYHIP_API int rayhip_scene_update_instances_blob(rayhip_ctx *ctx, const void *blob, size_t size, rayhip_camera *out_cam);
 
+/* Meshes that DEFORM in place (a skinned character, a cloth, a wave): new positions / normals / bitangents / uvs for vertices
+ * [first, first+count) of the uploaded scene; topology unchanged.  Everything that depends on positions is recomputed on the
+ * device (ray_amd/csrc/refit.h, refit.hip.h): the triangle records, the boxes of the bottom-level trees (refitted: the trees the
+ * upload made are kept, all of them, whatever the range), the per-triangle vertex table, the 4-wide collapse, the instance boxes
+ * and the top level (as rayhip_scene_update_instances rebuilds it).  Materials, lights, instances and textures stay.  The call
+ * waits for the context's stream first and returns when the device work is done; the accumulated image is the caller's to
+ * rayhip_clear.  Returns 0; 1 = error (a range outside the vertex array, a position of a vertex in use that is not finite -- both found before
+ * anything is copied; after any other error re-send the scene with rayhip_scene_upload); 2 = needs rayhip_scene_upload, nothing
+ * on the device was touched: no scene, a context that walks the 8-wide tree (its builder is host-only), a tree of more than 128
+ * levels, or a CHANGED vertex of a triangle light (lights are not rebuilt; a vertex of a light's triangle that arrives bytewise
+ * equal to what was uploaded is fine).  A triangle without area gets a record no ray can hit (their number goes into the
+ * RAYHIP_TRACE_UPLOAD trace; not an error); a triangle that had no area AT UPLOAD is not in the tree and stays absent, whatever
+ * its corners become. */
+/* new positions / normals / bitangents / uvs for vertices [first, first+count) of the uploaded scene; topology unchanged */
+RAYHIP_API int rayhip_scene_update_vertices(rayhip_ctx *ctx, uint32_t first_vertex, uint32_t count, const rayhip_vertex *vertices);
+/* the whole vertex array of a serialised scene of the same topology (scene_blob.h) */
+RAYHIP_API int rayhip_scene_update_vertices_blob(rayhip_ctx *ctx, const void *blob, size_t size);
+/* test hook: copy a device array of the acceleration structure to the host. which: 0 BVH2 nodes [0, nodes_used),
+ * 1 tris as 48-byte records (un-pitched), 2 tri_indices, 3 the live top-level leaves as (instance slot, lo.xyz, hi.xyz) 7 x 4 bytes each */
+RAYHIP_API int rayhip_k_read_accel(rayhip_ctx *ctx, int which, void *dst, size_t capacity_bytes, size_t *out_bytes);
+
 /* 1024-entry inverse filter CDF (RendererCPU.h:1234-1258 UpdateFilterTable; upload RendererVK.cpp:386-424) */
 RAYHIP_API int rayhip_set_filter_table(rayhip_ctx *ctx, const float *table, int count);
 

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <string>
 #include <unordered_map>
@@ -28,6 +29,7 @@
 #include "bvh_layout.h"
 #include "unet.h"
 #include "lbvh.hip.h"
+#include "refit.hip.h"
 #include "scene_blob.h"
 #include "scene_rebuild.h"
 #include "scene_update.h"

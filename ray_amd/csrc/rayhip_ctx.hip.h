@@ -152,6 +152,22 @@ struct rayhip_ctx {
     uint32_t tex_table[8] = {}, textures_count = 0, tex_flags = 0;
     struct { uint32_t vertices, vtx_indices, tri_materials, materials; } geometry = {};
     uint32_t instances_count = 0; // mesh instances on the device (scene_upload and scene_update set it)
+    // what rayhip_scene_update_vertices needs of the last full upload / instance update (refit.h)
+    struct Refit {
+        DevBuf level_nodes;                 // bottom-level BVH2 nodes sorted by height ...
+        std::vector<uint32_t> level_offset; // ... [level_offset[h - 1], level_offset[h]) are those of height h
+        int levels_rc = 2;                  // refit.h: plan_levels (2: a tree above 128 levels, or none planned)
+        DevBuf first_entry;                 // per triangle its lowest tris[] entry
+        DevBuf scratch;                     // [0] triangles without area of the last update; from byte 256: root indices, root nodes
+        uint32_t entries = 0;               // records in `tris`
+        std::vector<uint8_t> vertex_used;   // per vertex: some triangle of the table uses it (the array is a sparse pool)
+        uint32_t degenerate = 0;            // triangles without area the last update met
+        std::vector<uint32_t> roots;        // the distinct bottom-level roots as uploaded; the 4-wide node of roots[r] is r
+        std::unordered_map<uint32_t, uint32_t> ordinal_of_root;
+        std::vector<std::pair<uint32_t, rayhip_vertex>> light_vertices; // vertices that triangle lights use (ascending index), as uploaded
+        std::vector<uint32_t> live;                  // instance slots of the top level in place, ascending
+        std::vector<rayhip_mesh_instance> instances; // the instance array in place (device-side roots)
+    } refit;
     bool adaptive_dirty = false; // a pass ran with variance_threshold != 0 since the last Clear / Resize: required_samples may
                                  // lie below the next iteration, so passes are not batched (rayhip_render_batch)
     int lut_transform = 0, lut_dims = 0;

@@ -1,6 +1,7 @@
 // rayhip_upload.hip.h -- part of librayhip's host side (one translation unit: included by rayhip.hip, in this order, after the kernels):
 // scene upload: lights and derived tables, the scene view, rayhip_scene_upload (validation, leaf refinement, wide collapse),
-// rayhip_scene_update_instances (top level rebuilt on the device), filter table, tonemap LUT, the blob forms.
+// rayhip_scene_update_instances (top level rebuilt on the device), rayhip_scene_update_vertices (records, boxes, collapse and top level
+// recomputed on the device under the kept trees; refit.h), filter table, tonemap LUT, the blob forms, the hook rayhip_k_read_accel.
 #pragma once
 
 // the physical sky (rayhip_sky + its tables and textures: 1.6 MB): device copies and the view the kernels read; the directional-light
@@ -161,12 +162,25 @@ static uint32_t count_top_level_instances(const rayhip_bvh2_node *nodes, const u
     return uint32_t(seen.size());
 }
 
+// the part of the scene view that follows the top level: its root, the ray-sort grid over its bounds, the choice of the pooled kernel
+static void refresh_top_level_view(rayhip_ctx *c, const uint32_t tlas_root, const rayhip_lbvh::Box &root_box, const uint32_t live_instances) {
+    // the pooled closest-hit kernel hands prepared rays from lane to lane; a ray can change lanes only while nothing is pending at the top
+    // level, which is every ray of a scene with ONE instance (RAYHIP_POOL_ANY=1: the pooled kernel for any scene -- tests of its other path)
+    c->pool_scene = (live_instances == 1 || getenv("RAYHIP_POOL_ANY") != nullptr) && c->instances_count < (1u << 24);
+    c->sc.tlas_root = tlas_root;
+    // ray-sort grid: true bounds of the TLAS root (Scene::GetBounds takes fminf for the max corner, SceneCPU.cpp:1553)
+    for (int i = 0; i < 3; ++i) {
+        const bool have = root_box.lo[i] <= root_box.hi[i];
+        const float mn = have ? root_box.lo[i] : c->bbox_min[i], mx = have ? root_box.hi[i] : c->bbox_max[i];
+        const float ext = mx - mn;
+        c->sort_grid.root_min[i] = mn;
+        c->sort_grid.inv_cell[i] = (ext > 0.0f && ext < 1e30f) ? 256.0f / ext : 0.0f;
+    }
+}
+
 static void refresh_scene_view(rayhip_ctx *c, const rayhip_scene_desc *d, const uint32_t tlas_root, const rayhip_lbvh::Box &root_box,
                                const uint32_t live_instances) {
     SceneView &v = c->sc;
-    // the pooled closest-hit kernel hands prepared rays from lane to lane; a ray can change lanes only while nothing is pending at the top
-    // level, which is every ray of a scene with ONE instance (RAYHIP_POOL_ANY=1: the pooled kernel for any scene -- tests of its other path)
-    c->pool_scene = (live_instances == 1 || getenv("RAYHIP_POOL_ANY") != nullptr) && d->mesh_instances_count < (1u << 24);
     v.nodes = c->nodes.as<rayhip_bvh2_node>(), v.tris = c->tris.as<rayhip_tri_accel>(), v.tri_pitch = c->tri_pitch, v.all_solid = getenv("RAYHIP_NO_ALL_SOLID") ? 0u : c->all_solid;
     v.tri_indices = c->tri_indices.as<uint32_t>(), v.tri_materials = c->tri_materials.as<rayhip_tri_mat_data>();
     v.materials = c->materials.as<rayhip_material>(), v.vertices = c->vertices.as<rayhip_vertex>();
@@ -194,20 +208,118 @@ static void refresh_scene_view(rayhip_ctx *c, const rayhip_scene_desc *d, const 
     v.light_cwnodes_count = d->light_cwnodes_count;
     v.visible_lights_count = d->visible_lights_count;
     v.blocker_lights_count = d->blocker_lights_count;
-    v.tlas_root = tlas_root;
     v.env = d->env;
     v.sky = c->sky_view;
     memcpy(c->bbox_min, d->bbox_min, 12), memcpy(c->bbox_max, d->bbox_max, 12);
-    // ray-sort grid: true bounds of the TLAS root (Scene::GetBounds takes fminf for the max corner, SceneCPU.cpp:1553)
-    for (int i = 0; i < 3; ++i) {
-        const bool have = root_box.lo[i] <= root_box.hi[i];
-        const float mn = have ? root_box.lo[i] : d->bbox_min[i], mx = have ? root_box.hi[i] : d->bbox_max[i];
-        const float ext = mx - mn;
-        c->sort_grid.root_min[i] = mn;
-        c->sort_grid.inv_cell[i] = (ext > 0.0f && ext < 1e30f) ? 256.0f / ext : 0.0f;
-    }
+    refresh_top_level_view(c, tlas_root, root_box, live_instances);
 }
 
+
+// ---- what a later rayhip_scene_update_vertices needs of an upload (refit.h) -----------------------------------------------------
+// the bottom-level nodes sorted by height and the first entry of every triangle, on the device; the root list of the collapse; the
+// live instances and the instance array on the host.  `nodes` / `instances` / `tri_indices`: the arrays as uploaded.
+static int prepare_refit(rayhip_ctx *c, const rayhip_bvh2_node *nodes, const uint32_t nodes_count, const rayhip_mesh_instance *instances,
+                         const uint32_t instances_count, const uint32_t tlas_root, const uint32_t *tri_indices, const uint32_t entries,
+                         const uint32_t *vtx_indices, const uint32_t n_tris, const uint32_t n_vertices, const bool rebased_for_bvh8) {
+    rayhip_ctx::Refit &r = c->refit;
+    r.level_offset.clear(), r.roots.clear(), r.ordinal_of_root.clear(), r.live.clear();
+    r.levels_rc = 2, r.entries = entries, r.degenerate = 0;
+    // the vertices some triangle of the table uses: the vertex array is a sparse pool, a free slot may hold anything
+    r.vertex_used.assign(n_vertices, 0);
+    for (uint32_t e = 0; e < entries; ++e) {
+        for (uint32_t k = 0; tri_indices[e] < n_tris && k < 3; ++k) {
+            const uint32_t v = vtx_indices[size_t(tri_indices[e]) * 3 + k];
+            if (v < n_vertices) {
+                r.vertex_used[v] = 1;
+            }
+        }
+    }
+    r.instances.assign(instances, instances + instances_count);
+    std::vector<std::pair<uint32_t, uint32_t>> top;
+    if (tlas_root != 0xffffffffu && rayhip_rebuild::collect_leaf_ranges(nodes, nodes_count, tlas_root, top)) {
+        for (const auto &leaf : top) {
+            r.live.push_back(leaf.first);
+        }
+        std::sort(r.live.begin(), r.live.end());
+        r.live.erase(std::unique(r.live.begin(), r.live.end()), r.live.end());
+    }
+    if (rebased_for_bvh8) {
+        return 0; // (the 8-wide builder is host-only: such a context refuses the vertex update)
+    }
+    std::vector<uint32_t> root_of_instance;
+    if (!rayhip_bvh4::collect_roots(nodes, nodes_count, instances, instances_count, tlas_root, r.roots, root_of_instance)) {
+        r.roots.clear();
+    }
+    for (size_t k = 0; k < r.roots.size(); ++k) {
+        r.ordinal_of_root[r.roots[k]] = uint32_t(k);
+    }
+    std::vector<uint32_t> level_nodes;
+    r.levels_rc = rayhip_refit::plan_levels(nodes, nodes_count, r.roots, level_nodes, r.level_offset);
+    if (r.levels_rc != 0) {
+        return 0; // (a tree above 128 levels: the update says so when it is asked for)
+    }
+    const std::vector<uint32_t> first = rayhip_refit::first_entries(tri_indices, entries, n_tris);
+    if (upload(c, r.level_nodes, level_nodes.data(), level_nodes.size() * sizeof(uint32_t)) ||
+        upload(c, r.first_entry, first.data(), first.size() * sizeof(uint32_t)) ||
+        r.scratch.alloc(256 + r.roots.size() * (sizeof(uint32_t) + sizeof(rayhip_bvh2_node)) + 64)) {
+        return 1;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the two vectors go out of scope
+    return 0;
+}
+
+// the vertices some triangle light's triangle uses, as they are on the device: the light arrays are not rebuilt by a vertex update,
+// so it refuses to move one of these
+static void keep_light_vertices(rayhip_ctx *c, const rayhip_scene_desc *d) {
+    std::vector<std::pair<uint32_t, rayhip_vertex>> &kept = c->refit.light_vertices;
+    kept.clear();
+    for (uint32_t k = 0; k < d->li_indices_count; ++k) {
+        const uint32_t i = d->li_indices[k];
+        if (i >= d->lights_count || light_type(d->lights[i]) != LIGHT_TYPE_TRI) {
+            continue;
+        }
+        const size_t tri = float_as_uint(d->lights[i].params[0]);
+        for (size_t j = tri * 3; j < tri * 3 + 3 && j < d->vtx_indices_count; ++j) {
+            if (d->vtx_indices[j] < d->vertices_count) {
+                kept.emplace_back(d->vtx_indices[j], d->vertices[d->vtx_indices[j]]);
+            }
+        }
+    }
+    std::sort(kept.begin(), kept.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+    kept.erase(std::unique(kept.begin(), kept.end(), [](const auto &x, const auto &y) { return x.first == y.first; }), kept.end());
+}
+
+// The top level of `up` built ON THE DEVICE by the linear builder and written behind the uploaded nodes: two halves, used in turn --
+// the tree the scene view still points at is never overwritten, so a failure further down (rc 1) leaves a context that renders the
+// previous top level.  0 = ok, 1 = error, 2 = no room (a full upload reserves anew).
+static int rebuild_top_level(rayhip_ctx *c, const rayhip_update::Plan &up, uint32_t &tlas_root, rayhip_lbvh::Box &root_box) {
+    tlas_root = 0xffffffffu;
+    root_box = rayhip_lbvh::empty_box();
+    if (up.live.empty()) {
+        return 0;
+    }
+    const std::vector<uint32_t> group(up.live.size(), 0);
+    const rayhip_lbvh::Input ti = rayhip_update::top_level_input(up, group);
+    rayhip_lbvh::Output tlas;
+    std::string why;
+    if (!rayhip_lbvh::build_device(c->stream, ti, tlas, why)) {
+        return fail("top-level build failed: %s", why.c_str());
+    }
+    const uint32_t half = c->nodes_reserved / 2;
+    if (tlas.nodes.size() > half || tlas.group_root.empty() || tlas.group_root[0] == 0xffffffffu) {
+        (void)fail("no room for a top-level tree of %zu nodes", tlas.nodes.size());
+        return 2;
+    }
+    const uint32_t base = c->nodes_used + c->tlas_half * half;
+    c->tlas_half ^= 1u;
+    tlas_root = rayhip_update::relocate_top_level(tlas, up, base);
+    root_box = tlas.bounds;
+    // pending passes read the old tree: the caller flushed (RendererHIP) or synchronises through the stream order here
+    HIP_TRY(hipMemcpyAsync(c->nodes.as<rayhip_bvh2_node>() + base, tlas.nodes.data(), tlas.nodes.size() * sizeof(rayhip_bvh2_node),
+                           hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // `tlas` goes out of scope
+    return 0;
+}
 
 #define UPLOAD_TRACE(msg)                                                                                              \
     if (getenv("RAYHIP_TRACE_UPLOAD")) {                                                                               \
@@ -438,6 +550,11 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
         c->small_scene = wide != 0 && getenv("RAYHIP_NO_SMALL") == nullptr && wide_bytes + n_tris * sizeof(rayhip_tri_accel) <= (size_t(2) << 20);
         // the meshes in use, for rayhip_scene_update_instances: the roots of their trees as uploaded
         rayhip_update::collect_mesh_refs(n2, n2_count, mis, d->mesh_instances_count, tlas_root, wide ? blas_root4.data() : nullptr, c->mesh_refs);
+        // ... and for rayhip_scene_update_vertices: the bottom-level nodes by height, the live instances (refit.h)
+        if (prepare_refit(c, n2, n2_count, mis, d->mesh_instances_count, tlas_root, tri_indices_in, uint32_t(n_tris), d->vtx_indices,
+                          d->vtx_indices_count / 3, d->vertices_count, b8.ok && !b8.nodes.empty())) {
+            return 1;
+        }
     }
     UPLOAD_TRACE("bvh uploaded")
     UP(tri_materials)
@@ -475,6 +592,7 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
     if (upload_lights(c, d)) {
         return 1;
     }
+    keep_light_vertices(c, d);
     UPLOAD_TRACE("lights done")
     UP(textures)
     UP(texels)
@@ -584,31 +702,10 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
     }
     uint32_t tlas_root = 0xffffffffu;
     rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
-    if (!live.empty()) {
-        const std::vector<uint32_t> group(live.size(), 0);
-        const rayhip_lbvh::Input ti = rayhip_update::top_level_input(up, group);
-        rayhip_lbvh::Output tlas;
-        std::string why;
-        if (!rayhip_lbvh::build_device(c->stream, ti, tlas, why)) {
-            return fail("top-level build failed: %s", why.c_str());
-        }
-        // two halves, used in turn: the tree the scene view still points at is never overwritten, so a failure further
-        // down (rc 1) leaves a context that renders the previous top level
-        const uint32_t half = c->nodes_reserved / 2;
-        if (tlas.nodes.size() > half || tlas.group_root.empty() || tlas.group_root[0] == 0xffffffffu) {
-            (void)fail("no room for a top-level tree of %zu nodes", tlas.nodes.size());
-            return 2;
-        }
-        const uint32_t base = c->nodes_used + c->tlas_half * half;
-        c->tlas_half ^= 1u;
-        tlas_root = rayhip_update::relocate_top_level(tlas, up, base);
-        root_box = tlas.bounds;
-        UPLOAD_TRACE("top level built")
-        // pending passes read the old tree: the caller flushed (RendererHIP) or synchronises through the stream order here
-        HIP_TRY(hipMemcpyAsync(c->nodes.as<rayhip_bvh2_node>() + base, tlas.nodes.data(), tlas.nodes.size() * sizeof(rayhip_bvh2_node),
-                               hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream)); // `tlas` goes out of scope
+    if (const int rc = rebuild_top_level(c, up, tlas_root, root_box)) {
+        return rc;
     }
+    UPLOAD_TRACE("top level built")
     if (upload(c, c->mesh_instances, mis.data(), mis.size() * sizeof(rayhip_mesh_instance)) ||
         (c->wide && upload(c, c->blas_root4, root4.data(), root4.size() * sizeof(uint32_t)))) {
         return 1;
@@ -621,12 +718,14 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
             upload(c, c->env_qtree, d->env_qtree, size_t(d->env_qtree_count) * sizeof(float))) {
             return 1;
         }
+        keep_light_vertices(c, d);
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (upload_sky(c, d)) {
         return 1;
     }
     refresh_scene_view(c, d, tlas_root, root_box, uint32_t(live.size()));
+    c->refit.live = live, c->refit.instances = mis; // (what a later rayhip_scene_update_vertices rebuilds the top level over)
     UPLOAD_TRACE("instances updated")
     return 0;
 }
@@ -694,4 +793,240 @@ int rayhip_scene_update_instances_blob(rayhip_ctx *c, const void *blob, size_t s
         return fail("%s", err.c_str());
     }
     return rayhip_scene_update_instances(c, &d);
+}
+
+// ---- vertex update: meshes deform in place, the trees are kept and refitted on the device ----------------------------------------
+// Kept: tree topology, triangle order (tri_indices), materials, lights, instances.  Recomputed from the new positions, all in stream
+// order: the triangle records (k_refit_tris), the child boxes of every bottom-level BVH2 node (k_refit_level, one launch per height),
+// the per-triangle vertex table (k_fill_tri_verts), the 4-wide collapse over the same root list, the instance boxes (host, from the root
+// nodes read back) and the top level (the path of rayhip_scene_update_instances).  refit.h / refit.hip.h.
+int rayhip_scene_update_vertices(rayhip_ctx *c, uint32_t first_vertex, uint32_t count, const rayhip_vertex *vertices) {
+    if (use_device(c)) {
+        return 1;
+    }
+    rayhip_ctx::Refit &r = c->refit;
+    if (!c->have_scene) {
+        (void)fail("rayhip_scene_update_vertices before rayhip_scene_upload");
+        return 2;
+    }
+    if (c->wide == 8) {
+        (void)fail("rayhip_scene_update_vertices: the context walks the 8-wide tree, whose builder runs on the host only");
+        return 2;
+    }
+    if (r.levels_rc != 0) {
+        (void)fail("rayhip_scene_update_vertices: a bottom-level tree is higher than %u levels", rayhip_refit::MAX_LEVELS);
+        return 2;
+    }
+    if (uint64_t(first_vertex) + count > c->geometry.vertices || (count != 0 && vertices == nullptr)) {
+        return fail("rayhip_scene_update_vertices: vertices [%u, %u + %u) are outside the %u of the uploaded scene", first_vertex, first_vertex, count,
+                    c->geometry.vertices);
+    }
+    for (uint32_t i = 0; i < count; ++i) {
+        if (r.vertex_used[first_vertex + i] && (!std::isfinite(vertices[i].p[0]) || !std::isfinite(vertices[i].p[1]) || !std::isfinite(vertices[i].p[2]))) {
+            return fail("rayhip_scene_update_vertices: the position of vertex %u is not finite", first_vertex + i);
+        }
+    }
+    for (const auto &kept : r.light_vertices) { // (ascending; few)
+        if (kept.first >= first_vertex && kept.first - first_vertex < count &&
+            memcmp(&vertices[kept.first - first_vertex], &kept.second, sizeof(rayhip_vertex)) != 0) {
+            (void)fail("rayhip_scene_update_vertices: vertex %u belongs to a triangle light; lights are not rebuilt by this call", kept.first);
+            return 2;
+        }
+    }
+    const bool trace = getenv("RAYHIP_TRACE_UPLOAD") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    // a stamp waits for the device first, so that the phases can be told apart (only when tracing)
+#define VERTEX_TRACE(msg)                                                                                              \
+    if (trace) {                                                                                                       \
+        HIP_TRY(hipStreamSynchronize(c->stream));                                                                      \
+        fprintf(stderr, "rayhip_scene_update_vertices: %9.3f ms  %s\n",                                                \
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), msg);         \
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    VERTEX_TRACE("begin")
+    hipStream_t s = c->stream;
+    if (count) {
+        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + first_vertex, vertices, size_t(count) * sizeof(rayhip_vertex), hipMemcpyHostToDevice, s));
+    }
+    VERTEX_TRACE("vertices copied")
+    const uint32_t n_tris = c->geometry.vtx_indices / 3;
+    uint32_t *d_degenerate = r.scratch.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(d_degenerate, 0, sizeof(uint32_t), s));
+    if (r.entries) {
+        rayhip_refit::k_refit_tris<<<(r.entries + 255) / 256, 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(),
+                                                                           n_tris, c->tri_indices.as<uint32_t>(), r.first_entry.as<uint32_t>(), r.entries,
+                                                                           c->tris.as<float4>(), c->tri_pitch, d_degenerate);
+        HIP_TRY(hipGetLastError());
+    }
+    VERTEX_TRACE("triangle records")
+    for (size_t h = 1; h < r.level_offset.size(); ++h) {
+        const uint32_t n = r.level_offset[h] - r.level_offset[h - 1];
+        rayhip_refit::k_refit_level<<<(n + 255) / 256, 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), r.level_nodes.as<uint32_t>() + r.level_offset[h - 1], n,
+                                                                    c->tri_indices.as<uint32_t>(), c->vtx_indices.as<uint32_t>(), c->vertices.as<rayhip_vertex>());
+        HIP_TRY(hipGetLastError());
+    }
+    VERTEX_TRACE("boxes refitted")
+    if (n_tris) {
+        k_fill_tri_verts<<<(n_tris + 255) / 256, 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(), n_tris,
+                                                              c->tri_materials.as<rayhip_tri_mat_data>(), c->geometry.tri_materials, c->tri_verts.as<float4>(),
+                                                              c->tri_bitangents.as<float4>());
+        HIP_TRY(hipGetLastError());
+    }
+    VERTEX_TRACE("tri_verts done")
+    // the root node of every mesh in use -> the host; the count of triangles without area comes with them
+    std::vector<rayhip_bvh2_node> root_nodes(r.roots.size());
+    {
+        uint32_t *d_which = reinterpret_cast<uint32_t *>(r.scratch.as<uint8_t>() + 256);
+        rayhip_bvh2_node *d_roots = reinterpret_cast<rayhip_bvh2_node *>(r.scratch.as<uint8_t>() + 256 + ((r.roots.size() * sizeof(uint32_t) + 63) & ~size_t(63)));
+        if (!r.roots.empty()) {
+            HIP_TRY(hipMemcpyAsync(d_which, r.roots.data(), r.roots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            rayhip_refit::k_gather_nodes<<<unsigned((r.roots.size() + 255) / 256), 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), d_which, uint32_t(r.roots.size()),
+                                                                                               d_roots);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(root_nodes.data(), d_roots, r.roots.size() * sizeof(rayhip_bvh2_node), hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipMemcpyAsync(&r.degenerate, d_degenerate, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    // the 4-wide trees over the boxes just written: the same root list as at upload, so the wide node of roots[k] is k again
+    if (c->wide == 4 && !r.roots.empty()) {
+        uint32_t n_wide = 0;
+        std::string why;
+        bool unquantisable = false;
+        if (!rayhip_bvh4::build_device(s, c->nodes.as<rayhip_bvh2_node>(), c->nodes_used, r.roots, c->nodes4.as<Bvh4Node>(), n_wide, why, &unquantisable)) {
+            if (!unquantisable) {
+                return fail("4-wide collapse failed: %s", why.c_str());
+            }
+            // a box the grid cannot hold: the kernels walk the BVH2 from here on, as after an upload of such a scene
+            c->wide = 0, c->small_scene = false;
+            c->sc.nodes4 = nullptr, c->sc.blas_root4 = nullptr;
+            for (auto &ref : c->mesh_refs) {
+                ref.second.root4 = 0;
+            }
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    VERTEX_TRACE(c->wide == 4 ? "bvh4 built" : "no wide BLAS")
+    if (trace) {
+        fprintf(stderr, "rayhip_scene_update_vertices: %u triangles without area\n", r.degenerate);
+    }
+    // the top level over the new instance boxes: the live slots and the instance array of the last upload / instance update.  The leaf
+    // numbering is the one scene_update.h: plan documents (a leaf names the slot the host's leaf named); the box of a slot is made from
+    // that slot's own mesh and transform, which is what the walk follows the leaf to.
+    rayhip_update::Plan up;
+    up.live = r.live, up.instances = r.instances;
+    up.root4.assign(up.instances.size(), 0u);
+    for (const uint32_t mi : up.live) {
+        const auto it = mi < up.instances.size() ? r.ordinal_of_root.find(up.instances[mi].node_index) : r.ordinal_of_root.end();
+        if (it == r.ordinal_of_root.end()) {
+            return fail("rayhip_scene_update_vertices: instance %u has no tree on the device", mi);
+        }
+        up.root4[mi] = c->wide == 4 ? it->second : 0u;
+        up.boxes.push_back(rayhip_rebuild::transform_box(rayhip_rebuild::node_box(root_nodes[it->second]), up.instances[mi].xform));
+    }
+    if (c->wide == 4) {
+        for (auto &ref : c->mesh_refs) {
+            const auto it = r.ordinal_of_root.find(ref.second.node_index);
+            if (it != r.ordinal_of_root.end()) {
+                ref.second.root4 = it->second;
+            }
+        }
+        if (upload(c, c->blas_root4, up.root4.data(), up.root4.size() * sizeof(uint32_t))) {
+            return 1;
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    uint32_t tlas_root = 0xffffffffu;
+    rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
+    if (const int rc = rebuild_top_level(c, up, tlas_root, root_box)) {
+        return rc == 2 ? fail("rayhip_scene_update_vertices: %s", g_err.c_str()) : rc; // (the arrays are the new ones already: an error)
+    }
+    refresh_top_level_view(c, tlas_root, root_box, uint32_t(up.live.size()));
+    VERTEX_TRACE("top level built")
+#undef VERTEX_TRACE
+    return 0;
+}
+
+int rayhip_scene_update_vertices_blob(rayhip_ctx *c, const void *blob, size_t size) {
+    rayhip_scene_desc d;
+    rayhip_camera cam;
+    const float *ft = nullptr;
+    int ftn = 0;
+    std::string err;
+    if (!rayhip_blob::deserialize(blob, size, d, cam, &ft, &ftn, err, nullptr)) {
+        return fail("%s", err.c_str());
+    }
+    if (c && c->have_scene && (d.vertices_count != c->geometry.vertices || d.vtx_indices_count != c->geometry.vtx_indices)) {
+        return fail("rayhip_scene_update_vertices_blob: the blob holds %u vertices / %u indices, the uploaded scene %u / %u", d.vertices_count,
+                    d.vtx_indices_count, c->geometry.vertices, c->geometry.vtx_indices);
+    }
+    return rayhip_scene_update_vertices(c, 0, d.vertices_count, d.vertices);
+}
+
+// test hook: a device array of the acceleration structure -> the host
+int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_bytes, size_t *out_bytes) {
+    if (use_device(c)) {
+        return 1;
+    }
+    if (!c->have_scene || !out_bytes || (!dst && capacity_bytes)) {
+        return fail("rayhip_k_read_accel: no scene, or bad arguments");
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (which == 3) { // the leaves of the top level in place, by instance slot (what scene_update.h: plan reads from a host tree)
+        std::vector<rayhip_bvh2_node> nodes(size_t(c->nodes_used) + c->nodes_reserved);
+        HIP_TRY(hipMemcpy(nodes.data(), c->nodes.p, nodes.size() * sizeof(rayhip_bvh2_node), hipMemcpyDeviceToHost));
+        rayhip_scene_desc d = {};
+        d.nodes = nodes.data(), d.nodes_count = uint32_t(nodes.size());
+        std::vector<std::pair<uint32_t, rayhip_lbvh::Box>> leaves;
+        if (c->sc.tlas_root != 0xffffffffu && !rayhip_rebuild::collect_leaf_boxes(d, c->sc.tlas_root, leaves)) {
+            return fail("rayhip_k_read_accel: the top level on the device is malformed");
+        }
+        std::sort(leaves.begin(), leaves.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+        std::vector<uint32_t> out;
+        for (const auto &l : leaves) {
+            const bool real = l.second.lo[0] <= l.second.hi[0] && l.second.lo[1] <= l.second.hi[1] && l.second.lo[2] <= l.second.hi[2];
+            rayhip_lbvh::Box b = real ? l.second : rayhip_lbvh::empty_box();
+            if (out.size() >= 7 && out[out.size() - 7] == l.first) { // (a lone instance is stored as both children of the root)
+                if (!real) {
+                    continue;
+                }
+                rayhip_lbvh::Box prev;
+                memcpy(&prev, &out[out.size() - 6], sizeof(prev));
+                rayhip_lbvh::grow(b, prev);
+                out.resize(out.size() - 7);
+            }
+            out.push_back(l.first);
+            out.resize(out.size() + 6);
+            memcpy(&out[out.size() - 6], &b, sizeof(b));
+        }
+        *out_bytes = out.size() * sizeof(uint32_t);
+        if (*out_bytes > capacity_bytes) {
+            return fail("rayhip_k_read_accel: %zu bytes do not fit %zu", *out_bytes, capacity_bytes);
+        }
+        memcpy(dst, out.data(), *out_bytes);
+        return 0;
+    }
+    const void *src = nullptr;
+    size_t bytes = 0;
+    if (which == 0) {
+        src = c->nodes.p, bytes = size_t(c->nodes_used) * sizeof(rayhip_bvh2_node);
+    } else if (which == 1) {
+        src = c->tris.p, bytes = size_t(c->refit.entries) * sizeof(rayhip_tri_accel);
+    } else if (which == 2) {
+        src = c->tri_indices.p, bytes = size_t(c->refit.entries) * sizeof(uint32_t);
+    } else {
+        return fail("rayhip_k_read_accel: no array %d", which);
+    }
+    *out_bytes = bytes;
+    if (bytes > capacity_bytes) {
+        return fail("rayhip_k_read_accel: %zu bytes do not fit %zu", bytes, capacity_bytes);
+    }
+    if (bytes == 0) {
+        return 0;
+    }
+    if (which == 1 && c->tri_pitch != 3) { // the table was re-pitched to 64 bytes per record: the first 48 of each
+        HIP_TRY(hipMemcpy2D(dst, sizeof(rayhip_tri_accel), src, size_t(c->tri_pitch) * 16, sizeof(rayhip_tri_accel), c->refit.entries, hipMemcpyDeviceToHost));
+    } else {
+        HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    }
+    return 0;
 }

@@ -87,18 +87,20 @@ SHADOW_RAY_DTYPE = np.dtype([("o", "<f4", 3), ("depth", "<u4"), ("d", "<f4", 3),
                              ("xy", "<u4")])
 HIT_DTYPE = np.dtype([("obj_index", "<i4"), ("prim_index", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4")])
 assert RAY_DTYPE.itemsize == 72 and SHADOW_RAY_DTYPE.itemsize == 48 and HIT_DTYPE.itemsize == 20
+VERTEX_DTYPE = np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("b", "<f4", 3), ("t", "<f4", 2)])  # rayhip_vertex
+assert VERTEX_DTYPE.itemsize == 44
 
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
     "unet_init", "denoise_unet", "unet_set_precision", "unet_read_tensor",
     "export_shard_device", "owned_bytes", "export_owned", "import_owned", "finish_import",
     "cache_enable", "cache_resolve", "cache_reset", "cache_readback", "k_cache_begin_paths", "k_cache_update_vertices", "k_cache_query",
-    "k_lbvh_build", "k_bvh4_collapse", "k_bvh4_test_nodes",
+    "k_lbvh_build", "k_bvh4_collapse", "k_bvh4_test_nodes", "k_read_accel",
 )
 
 
@@ -188,6 +190,9 @@ class Library:
             f("k_lbvh_build").argtypes = [vp, vp, vp, u32, u32, u32, C.c_int, C.c_int, C.c_int, vp, u32, vp, u32, vp, vp, vp]
             f("k_bvh4_collapse").argtypes = [vp, vp, u32, vp, u32, vp, vp, vp]
             f("k_bvh4_test_nodes").argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp]
+            f("scene_update_vertices").argtypes = [vp, u32, u32, vp]
+            f("scene_update_vertices_blob").argtypes = [vp, vp, C.c_size_t]
+            f("k_read_accel").argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -279,6 +284,40 @@ class Context:
         self.L.check(rc)
         self.cam = cam
         return 0
+
+    def update_vertices(self, first: int, array: np.ndarray) -> int:
+        """new vertices [first, first + len(array)) of the uploaded scene (VERTEX_DTYPE records, or [n][11] float32: position, normal,
+        bitangent, uv); the trees are refitted on the device (rayhip_scene_update_vertices).  Returns 0, or 2 if the change needs a
+        full upload_scene_blob(); an error raises."""
+        array = np.ascontiguousarray(array)
+        if array.dtype != VERTEX_DTYPE:
+            array = np.ascontiguousarray(array, dtype=np.float32).reshape(-1, 11)
+        rc = self.L.fn("scene_update_vertices")(self._ctx, int(first), len(array), array.ctypes.data)
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def update_vertices_blob(self, blob: bytes) -> int:
+        """the vertex array of `blob`, a scene of the topology that is on the device (rayhip_scene_update_vertices_blob); returns as
+        update_vertices()"""
+        b = blob if isinstance(blob, np.ndarray) else _aligned_copy(blob)  # (an array: uint8, 16-byte aligned -- a caller that sends a scene repeatedly)
+        assert b.dtype == np.uint8 and b.ctypes.data % 16 == 0
+        rc = self.L.fn("scene_update_vertices_blob")(self._ctx, b.ctypes.data, b.size)
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def read_accel(self, which: int) -> np.ndarray:
+        """test hook (rayhip_k_read_accel): 0 the BVH2 nodes [n][16] u32 words, 1 the triangle records [n][12] f32, 2 tri_indices [n] u32,
+        3 the live top-level leaves [n][7] u32 words (instance slot, lo.xyz, hi.xyz as float bits), by slot"""
+        n = C.c_size_t(0)
+        self.L.fn("k_read_accel")(self._ctx, which, None, 0, C.byref(n))  # (refused: the size comes back)
+        buf = np.zeros(max(int(n.value), 4) // 4, dtype=np.uint32)
+        self.L.check(self.L.fn("k_read_accel")(self._ctx, which, buf.ctypes.data, buf.nbytes, C.byref(n)))
+        buf = buf[:n.value // 4]
+        return {0: lambda: buf.reshape(-1, 16), 1: lambda: buf.view(np.float32).reshape(-1, 12), 2: lambda: buf, 3: lambda: buf.reshape(-1, 7)}[which]()
 
     def render(self, iteration: int, rect=None, cam: Camera = None, flags: int = 0, stats: Stats = None):
         rect = (0, 0, self.w, self.h) if rect is None else rect
