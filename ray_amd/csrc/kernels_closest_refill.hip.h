@@ -29,11 +29,15 @@
 // secondary bounces (K2 2.25 -> 2.05 ms), bit-identical frames.  That is the default now (rayhip.hip: RAYHIP_REFILL=2).
 // RT_REFILL_MIN (lanes waiting before the wavefront leaves the BLAS loop to serve them): 16: 2.15, 24: 2.06, 32: 2.07,
 // 40: 2.04 ms.
+// Round 9 (profiles/r09; bit-identical frames): this unit is built without the SLP vectoriser -- it packed the triangle test into half-rate
+// v_pk_mul_f32 / v_pk_add_f32 and paired their operands with v_mov (30 packed and 14 moves in the loop, 16 bytes of scratch; now none) -- and
+// the loop header takes each ballot from one vector compare and votes on 32-bit scalar counts (2 vector instructions, were 7).  Traced run,
+// parent -> flag -> both: secondary 548.5 -> 533.1 -> 526.5 ms, primary 99.0 -> 94.3 -> 91.5 ms; headline 759.5 -> 776.8 Msamples/s.
 #ifndef RT_REFILL_MIN
 #define RT_REFILL_MIN 40
 #endif
 #ifndef RT_REFILL_MIN_WAVES
-#define RT_REFILL_MIN_WAVES 6 // 80 VGPRs, 40 bytes of scratch.  Round 2: 5 (96 VGPRs; 6 spilled in the loop and lost).  With round 3's shorter node
+#define RT_REFILL_MIN_WAVES 6 // 80 VGPRs, no scratch (round 9; 40 bytes in round 3).  Round 2: 5 (96 VGPRs; 6 spilled in the loop and lost).  With round 3's shorter node
                               // test 6 wins: K2 1.92 against 2.02 ms per iteration; 7 (72 VGPRs, 76 bytes of scratch) 2.26
 #endif
 // MIN_WAIT: lanes that must be waiting before the wavefront leaves the BLAS loop to serve them.  RT_REFILL_MIN for the incoherent
@@ -127,11 +131,16 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
         // ---- BLAS part: the majority-scheduled walk of rt_bvh4.h over the lanes that are inside an instance; left as soon
         // as RT_REFILL_MIN lanes wait outside for the service part below
         for (;;) {
-            const bool in_blas = (lvl == BLAS);
             // (the sentinel never stays in `cur`: leave_blas)
-            const bool at_leaf = in_blas && (WIDE == 8 ? (l0 | l1) != 0u : (cur & BVH2_PRIM_COUNT_BITS) != 0);
-            const bool at_node = in_blas && !at_leaf;
-            const int n_node = __popcll(__ballot(at_node)), n_leaf = __popcll(__ballot(at_leaf));
+            // Each ballot takes ONE vector compare, whose SGPR result is the mask; the masks are combined and counted on the scalar unit.
+            // A ballot of a combined predicate (in_blas && ...) is materialised lane by lane first (v_cndmask 0 / 1, v_cmp_ne), twice
+            // per iteration, and 64-bit counts put the vote onto the vector unit (there is no scalar 64-bit less-than): round 9
+            const bool in_blas = (lvl == BLAS);
+            const bool leaf_word = (WIDE == 8 ? (l0 | l1) != 0u : (cur & BVH2_PRIM_COUNT_BITS) != 0);
+            const unsigned long long m_blas = __builtin_amdgcn_ballot_w64(in_blas), m_leaf_word = __builtin_amdgcn_ballot_w64(leaf_word);
+            const bool at_leaf = in_blas && leaf_word;
+            const bool at_node = in_blas && !leaf_word;
+            const int n_node = uniform_count(m_blas & ~m_leaf_word), n_leaf = uniform_count(m_blas & m_leaf_word);
             const int n_out = WAVE - n_node - n_leaf - int(n_dead);
 #ifdef RT_PROFILE_TRACE
             st_a += n_node, st_b += n_leaf, st_iter += 1;

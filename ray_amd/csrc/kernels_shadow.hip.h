@@ -122,10 +122,13 @@ __global__ void __launch_bounds__(WAVE, RT_SHADOW_REFILL_MIN_WAVES) k_trace_shad
     for (;;) {
         // ---- BLAS part: majority-scheduled node / leaf steps over the lanes inside an instance
         for (;;) {
+            // (one vector compare per ballot, masks combined and counted on the scalar unit: kernels_closest_refill.hip.h)
             const bool in_blas = (lvl == BLAS);
-            const bool at_leaf = in_blas && (cur & BVH2_PRIM_COUNT_BITS) != 0;
-            const bool at_node = in_blas && !at_leaf;
-            const int n_node = __popcll(__ballot(at_node)), n_leaf = __popcll(__ballot(at_leaf));
+            const bool leaf_word = (cur & BVH2_PRIM_COUNT_BITS) != 0;
+            const unsigned long long m_blas = __builtin_amdgcn_ballot_w64(in_blas), m_leaf_word = __builtin_amdgcn_ballot_w64(leaf_word);
+            const bool at_leaf = in_blas && leaf_word;
+            const bool at_node = in_blas && !leaf_word;
+            const int n_node = uniform_count(m_blas & ~m_leaf_word), n_leaf = uniform_count(m_blas & m_leaf_word);
             const int n_out = WAVE - n_node - n_leaf - int(n_dead);
             if (n_node + n_leaf == 0 || n_out >= MIN_WAIT) {
                 break;

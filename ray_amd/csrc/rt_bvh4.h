@@ -53,6 +53,8 @@ static_assert(sizeof(Bvh4Node) == 64, "Bvh4Node must be one 64-byte fetch unit")
 
 constexpr uint32_t BVH4_SENTINEL = 0x1fffffffu; // same stack sentinel as the BVH2 walk (never a node index)
 constexpr uint32_t BVH4_EMPTY = 0xffffffffu;    // unused child slot
+// (the walk loops tell node, sentinel and leaf word apart by one compare each: every word with a count bit lies above the sentinel)
+static_assert(BVH4_SENTINEL + 1u == (BVH2_PRIM_COUNT_BITS & (0u - BVH2_PRIM_COUNT_BITS)), "the sentinel is the largest word without a count bit");
 
 // one de-quantised box coordinate: a single fused multiply-add, the same operation on host (builder check) and device
 RT_HD float bvh4_dequant(const uint32_t q, const float scale, const float org) { return __builtin_fmaf(float(q), scale, org); }
@@ -192,6 +194,18 @@ RT_HD void bvh4_visit(const Bvh4Node *nodes4, const f3 ro, const f3 inv_d, const
     }
 }
 
+#if defined(__HIPCC__)
+// lanes in a ballot mask as a 32-bit scalar.  The empty asm pins the count to an SGPR of that width: left alone, the compiler compares the
+// counts as the 64-bit values the population count produced, and a 64-bit less-than exists on the vector unit only
+__device__ __forceinline__ int uniform_count(const unsigned long long mask) {
+    int n = __builtin_popcountll(mask);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(n));
+#endif
+    return n;
+}
+#endif
+
 // Ordered walk over a 4-wide BLAS.  `leaf(word)` gets a reference leaf word and returns true to stop (any-hit early
 // out).  `t_ref` is re-read at every node so that hits found in earlier leaves prune.
 //
@@ -220,9 +234,10 @@ RT_HD bool walk_bvh4(const Bvh4Node *nodes4, const uint32_t root, const f3 ro, c
     // and leaf tests is unchanged, so are the results.  Measured (Bistro-class, 1080p): lanes busy in a node visit
     // 28 % -> 48 %, closest-hit kernel 3.21 -> 2.83 ms.
     for (;;) {
-        const bool at_node = (cur & BVH2_PRIM_COUNT_BITS) == 0 && cur != BVH4_SENTINEL;
-        const bool at_leaf = (cur & BVH2_PRIM_COUNT_BITS) != 0;
-        const int n_node = __popcll(__ballot(at_node)), n_leaf = __popcll(__ballot(at_leaf));
+        // node indices lie below the sentinel, leaf words (a count bit set) above it: one compare each, whose mask is the ballot
+        const bool at_node = cur < BVH4_SENTINEL;
+        const bool at_leaf = cur > BVH4_SENTINEL;
+        const int n_node = uniform_count(__builtin_amdgcn_ballot_w64(at_node)), n_leaf = uniform_count(__builtin_amdgcn_ballot_w64(at_leaf));
         if (n_node == 0 && n_leaf == 0) {
             break;
         }

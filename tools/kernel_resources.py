@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Register / scratch / occupancy table of every kernel in librayhip (hipcc -Rpass-analysis=kernel-resource-usage).
+Each unit is compiled with the flags __graft_entry__.build() gives it, so the table is that of the shipped library.
 Usage: python tools/kernel_resources.py [extra hipcc flags...]   (CPU only: the compiler reports the numbers)"""
-import os, re, subprocess, sys
+import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-base = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wno-unused-function",
-        "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/_kr.o"] + sys.argv[1:]
+sys.path.insert(0, ROOT)
+import __graft_entry__ as g
 out = ""
-for src, extra in (("rayhip.hip", []), ("shade_kernels.hip", [])):
-    out += subprocess.run(base + extra + ["-c", src], cwd=os.path.join(ROOT, "ray_amd", "csrc"), capture_output=True, text=True).stderr
+with tempfile.TemporaryDirectory() as td:
+    tail = ["-Rpass-analysis=kernel-resource-usage", "-o", os.path.join(td, "_kr.o")] + sys.argv[1:]
+    for src, flags in (("rayhip.hip", g.RAYHIP_FLAGS), ("shade_kernels.hip", g.HIPCC_FLAGS)):
+        out += subprocess.run([g._hipcc(), *[f for f in flags if f != "-Wall"], *tail, "-c", src], cwd=os.path.join(ROOT, "ray_amd", "csrc"), capture_output=True,
+                              text=True).stderr
 cur = None
 rows = {}
 for line in out.splitlines():

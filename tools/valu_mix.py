@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static vector-instruction mix of the closest-hit kernel's walk loop -> profiles/<round>/k2_valu_mix.json.
 
-    python tools/valu_mix.py [out.json]        (here, no GPU: hipcc -S of ray_amd/csrc/rayhip.hip, ~30 s)
+    python tools/valu_mix.py [out.json]        (here, no GPU: hipcc -S of ray_amd/csrc/rayhip.hip with the flags it is built with, ~30 s)
 
 Classes and their issue costs are those tools/valu_bench.hip measured on the MI355X (profiles/r03/valu_bench.txt, 8 waves per SIMD):
   full     2.3 SIMD cycles per wave-instruction   v_mul / add / sub / fmac_f32, logic, shifts, v_mov, v_add_u32 ...
@@ -96,7 +96,7 @@ def main():
     csrc = os.path.join(ROOT, "ray_amd", "csrc")
     with tempfile.TemporaryDirectory() as td:
         s_path = os.path.join(td, "rayhip.s")
-        subprocess.run([g._hipcc(), *[f for f in g.HIPCC_FLAGS if f not in ("-fPIC",)], "--cuda-device-only", "-S", "rayhip.hip", "-o", s_path], cwd=csrc, check=True,
+        subprocess.run([g._hipcc(), *[f for f in g.RAYHIP_FLAGS if f not in ("-fPIC",)], "--cuda-device-only", "-S", "rayhip.hip", "-o", s_path], cwd=csrc, check=True,
                        stderr=subprocess.DEVNULL)
         asm = open(s_path).read()
     mix, ops, n_blocks = kernel_loop_mix(asm, "_ZN2rt22k_trace_closest_refillILi4ELi40EEE")

@@ -35,7 +35,7 @@ def build_one(name, flags):
     trace_only = [f[7:] for f in flags if f.startswith("+trace:")]  # "+trace:<flag>": for rayhip.hip only
     flags = [f for f in flags if not f.startswith("+")]
     base = [f for f in g.HIPCC_FLAGS if not (f.startswith("-ffp-contract") and any(x.startswith("-ffp-contract") for x in flags))]
-    objs = {"rayhip": ("rayhip.hip", trace_only),
+    objs = {"rayhip": ("rayhip.hip", [f for f in g.RAYHIP_FLAGS if f not in g.HIPCC_FLAGS] + trace_only),  # (the unit's own flags of the build)
             "shade": ("shade_kernels.hip", shade_only)}
     class R:
         stderr = ""
