@@ -423,8 +423,41 @@ RAYHIP_API int rayhip_scene_update_instances_blob(rayhip_ctx *ctx, const void *b
 RAYHIP_API int rayhip_scene_update_vertices(rayhip_ctx *ctx, uint32_t first_vertex, uint32_t count, const rayhip_vertex *vertices);
 /* the whole vertex array of a serialised scene of the same topology (scene_blob.h) */
 RAYHIP_API int rayhip_scene_update_vertices_blob(rayhip_ctx *ctx, const void *blob, size_t size);
+/* The same update from vertices that are ALREADY ON THE DEVICE (the caller's own kernels, a tensor): `device_vertices` points at
+ * `count` records in device memory of the context's device, complete when the call is made.  They are checked there (a kernel, two
+ * counters read back), then copied device to device and refitted as above.  Returns as rayhip_scene_update_vertices: 1 for a range
+ * outside the array or a position of a vertex in use that is not finite, 2 for a changed vertex of a triangle light -- both found
+ * before the vertex array is written. */
+RAYHIP_API int rayhip_scene_update_vertices_device(rayhip_ctx *ctx, uint32_t first_vertex, uint32_t count, const rayhip_vertex *device_vertices);
+
+/* SKINS: the deformation itself on the device (ray_amd/csrc/skin.h, skin.hip.h).  A skin keeps the rest pose and the influences of
+ * a vertex range on the device; a pose is one palette of bone matrices per skin -- bones_count row-major 3x4 floats (12 per bone)
+ * that act in the mesh's object space, the instance transforms stay on top.  Linear-blend skinning with four influences per
+ * vertex: positions under the whole matrix; normals and bitangents under its 3x3 part (no inverse-transpose: exact for rigid bones
+ * and uniform scale) and normalised; uvs copied; a vertex whose four weights are zero keeps its rest record.  A pose always starts
+ * from the rest pose: poses do not accumulate.  rayhip_scene_pose_skins poses all named skins (palettes[i] belongs to skins[i]) into
+ * a staging array and refits ONCE, as rayhip_scene_update_vertices does.  Up to 16 skins are live per context, over disjoint
+ * ranges; every rayhip_scene_upload[_blob] discards them all.  *out_skin is a handle of 16 or more -- never one of the return
+ * codes -- and the handle of a destroyed or discarded skin names no later one.
+ * Return values as rayhip_scene_update_vertices.  2 = needs rayhip_scene_upload, nothing touched: no scene, a skin id that is not
+ * live, the 8-wide tree, a tree of more than 128 levels, or (at create time) a range that holds a vertex of a triangle light.
+ * 1 = error: a range outside the array or overlapping a live skin, a bone index >= bones_count, a negative or non-finite weight,
+ * a null pointer, a seventeenth skin, or a posed position of a vertex in use that is not finite (found before the vertex array is
+ * written). */
+typedef struct rayhip_skin_desc {
+    uint32_t first_vertex, count;      /* range of the uploaded vertex array this skin drives */
+    const rayhip_vertex *rest;         /* count rest-pose records; NULL = what the device holds for the range now */
+    const uint16_t *bone_indices;      /* count x 4 */
+    const float *bone_weights;         /* count x 4 */
+    uint32_t bones_count;
+} rayhip_skin_desc;
+RAYHIP_API int rayhip_skin_create(rayhip_ctx *ctx, const rayhip_skin_desc *desc, int *out_skin);
+RAYHIP_API int rayhip_skin_destroy(rayhip_ctx *ctx, int skin);
+RAYHIP_API int rayhip_scene_pose_skins(rayhip_ctx *ctx, int n, const int *skins, const float *const *palettes); /* palettes[i]: bones_count x 12 */
+
 /* test hook: copy a device array of the acceleration structure to the host. which: 0 BVH2 nodes [0, nodes_used),
- * 1 tris as 48-byte records (un-pitched), 2 tri_indices, 3 the live top-level leaves as (instance slot, lo.xyz, hi.xyz) 7 x 4 bytes each */
+ * 1 tris as 48-byte records (un-pitched), 2 tri_indices, 3 the live top-level leaves as (instance slot, lo.xyz, hi.xyz) 7 x 4 bytes each,
+ * 4 the vertex array as 44-byte records */
 RAYHIP_API int rayhip_k_read_accel(rayhip_ctx *ctx, int which, void *dst, size_t capacity_bytes, size_t *out_bytes);
 
 /* 1024-entry inverse filter CDF (RendererCPU.h:1234-1258 UpdateFilterTable; upload RendererVK.cpp:386-424) */

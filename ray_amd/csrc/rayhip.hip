@@ -30,6 +30,7 @@
 #include "unet.h"
 #include "lbvh.hip.h"
 #include "refit.hip.h"
+#include "skin.hip.h"
 #include "scene_blob.h"
 #include "scene_rebuild.h"
 #include "scene_update.h"

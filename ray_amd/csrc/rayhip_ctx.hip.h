@@ -167,7 +167,32 @@ struct rayhip_ctx {
         std::vector<std::pair<uint32_t, rayhip_vertex>> light_vertices; // vertices that triangle lights use (ascending index), as uploaded
         std::vector<uint32_t> live;                  // instance slots of the top level in place, ascending
         std::vector<rayhip_mesh_instance> instances; // the instance array in place (device-side roots)
+        // ... and what the updates that never see the vertices on the host check on the device (skin.hip.h)
+        DevBuf d_vertex_used;                     // vertex_used
+        DevBuf d_light_index, d_light_vertices;   // light_vertices as two arrays
     } refit;
+    // skins (rayhip_skin_create, skin.h): rest pose and influences of a vertex range, on the device until the next scene upload
+    struct Skin {
+        bool live = false;
+        int id = 0; // the handle the caller holds: (serial << 4) | slot, so a handle of a discarded skin never names a later one
+        uint32_t first = 0, count = 0, bones_count = 0;
+        DevBuf rest, indices, weights; // rayhip_vertex [count], uint16 [count][4], float [count][4]
+    } skins[rayhip_skin::MAX_SKINS];
+    uint32_t skin_serial = 0;
+    // the live skin handle `id` names, or null
+    Skin *skin_of(const int id) {
+        Skin &k = skins[id & int(rayhip_skin::MAX_SKINS - 1)];
+        return id > 0 && k.live && k.id == id ? &k : nullptr;
+    }
+    DevBuf skin_stage;    // the posed vertices of one rayhip_scene_pose_skins call, skin after skin (sized to the largest call seen)
+    DevBuf skin_palettes; // ... and its palettes
+    DevBuf skin_counters; // [0] used vertices without a finite position, [1] changed light vertices
+    void discard_skins() {
+        for (Skin &k : skins) {
+            k.live = false;
+            k.rest.release(), k.indices.release(), k.weights.release();
+        }
+    }
     bool adaptive_dirty = false; // a pass ran with variance_threshold != 0 since the last Clear / Resize: required_samples may
                                  // lie below the next iteration, so passes are not batched (rayhip_render_batch)
     int lut_transform = 0, lut_dims = 0;
@@ -783,6 +808,10 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
         }
     }
     c->stack_spill2.release();
+    c->discard_skins();
+    for (DevBuf *b : {&c->skin_stage, &c->skin_palettes, &c->skin_counters, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices}) {
+        b->release();
+    }
     for (hipEvent_t e : c->events) {
         (void)hipEventDestroy(e);
     }

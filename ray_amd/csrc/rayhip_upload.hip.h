@@ -1,7 +1,8 @@
 // rayhip_upload.hip.h -- part of librayhip's host side (one translation unit: included by rayhip.hip, in this order, after the kernels):
 // scene upload: lights and derived tables, the scene view, rayhip_scene_upload (validation, leaf refinement, wide collapse),
 // rayhip_scene_update_instances (top level rebuilt on the device), rayhip_scene_update_vertices (records, boxes, collapse and top level
-// recomputed on the device under the kept trees; refit.h), filter table, tonemap LUT, the blob forms, the hook rayhip_k_read_accel.
+// recomputed on the device under the kept trees; refit.h) and its siblings that never see the vertices on the host (rayhip_skin_create /
+// rayhip_scene_pose_skins, rayhip_scene_update_vertices_device; skin.h), filter table, tonemap LUT, the blob forms, the hook rayhip_k_read_accel.
 #pragma once
 
 // the physical sky (rayhip_sky + its tables and textures: 1.6 MB): device copies and the view the kernels read; the directional-light
@@ -289,6 +290,24 @@ static void keep_light_vertices(rayhip_ctx *c, const rayhip_scene_desc *d) {
     kept.erase(std::unique(kept.begin(), kept.end(), [](const auto &x, const auto &y) { return x.first == y.first; }), kept.end());
 }
 
+// ... and on the device, with the per-vertex `used` flags, for the updates whose vertices never pass through the host
+// (k_skin_vertices, k_check_vertices: skin.hip.h).  `with_used`: the flags too (they change with an upload only).
+static int upload_vertex_checks(rayhip_ctx *c, const bool with_used) {
+    rayhip_ctx::Refit &r = c->refit;
+    std::vector<uint32_t> index(r.light_vertices.size());
+    std::vector<rayhip_vertex> kept(r.light_vertices.size());
+    for (size_t k = 0; k < r.light_vertices.size(); ++k) {
+        index[k] = r.light_vertices[k].first, kept[k] = r.light_vertices[k].second;
+    }
+    if (upload(c, r.d_light_index, index.data(), index.size() * sizeof(uint32_t)) ||
+        upload(c, r.d_light_vertices, kept.data(), kept.size() * sizeof(rayhip_vertex)) ||
+        (with_used && upload(c, r.d_vertex_used, r.vertex_used.data(), r.vertex_used.size()))) {
+        return 1;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the two vectors go out of scope
+    return 0;
+}
+
 // The top level of `up` built ON THE DEVICE by the linear builder and written behind the uploaded nodes: two halves, used in turn --
 // the tree the scene view still points at is never overwritten, so a failure further down (rc 1) leaves a context that renders the
 // previous top level.  0 = ok, 1 = error, 2 = no room (a full upload reserves anew).
@@ -338,6 +357,7 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
     const auto upload_t0 = std::chrono::steady_clock::now();
     (void)upload_t0;
     UPLOAD_TRACE("begin")
+    c->discard_skins(); // (a skin names a range of the vertex array this call replaces)
     const rayhip_layout::AlignedDesc aligned(*d_in); // see bvh_layout.h
     const rayhip_scene_desc *d = &aligned.d;
     if (d->env.qtree_levels < 0 || d->env.qtree_levels > 16) {
@@ -593,6 +613,9 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
         return 1;
     }
     keep_light_vertices(c, d);
+    if (upload_vertex_checks(c, true)) {
+        return 1;
+    }
     UPLOAD_TRACE("lights done")
     UP(textures)
     UP(texels)
@@ -719,6 +742,9 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
             return 1;
         }
         keep_light_vertices(c, d);
+        if (upload_vertex_checks(c, false)) {
+            return 1;
+        }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (upload_sky(c, d)) {
@@ -795,6 +821,17 @@ int rayhip_scene_update_instances_blob(rayhip_ctx *c, const void *blob, size_t s
     return rayhip_scene_update_instances(c, &d);
 }
 
+// the stamps of the vertex updates (RAYHIP_TRACE_UPLOAD): a stamp waits for the device first, so that the phases can be told apart (only when tracing)
+#define VERTEX_TRACE_AS(who, msg)                                                                                      \
+    if (trace) {                                                                                                       \
+        HIP_TRY(hipStreamSynchronize(c->stream));                                                                      \
+        fprintf(stderr, who ": %9.3f ms  %s\n",                                                                        \
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), msg);         \
+    }
+#define VERTEX_TRACE(msg) VERTEX_TRACE_AS("rayhip_scene_update_vertices", msg)
+
+static int refit_after_vertices(rayhip_ctx *c, bool trace, std::chrono::steady_clock::time_point t0);
+
 // ---- vertex update: meshes deform in place, the trees are kept and refitted on the device ----------------------------------------
 // Kept: tree topology, triangle order (tri_indices), materials, lights, instances.  Recomputed from the new positions, all in stream
 // order: the triangle records (k_refit_tris), the child boxes of every bottom-level BVH2 node (k_refit_level, one launch per height),
@@ -835,20 +872,20 @@ int rayhip_scene_update_vertices(rayhip_ctx *c, uint32_t first_vertex, uint32_t 
     }
     const bool trace = getenv("RAYHIP_TRACE_UPLOAD") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    // a stamp waits for the device first, so that the phases can be told apart (only when tracing)
-#define VERTEX_TRACE(msg)                                                                                              \
-    if (trace) {                                                                                                       \
-        HIP_TRY(hipStreamSynchronize(c->stream));                                                                      \
-        fprintf(stderr, "rayhip_scene_update_vertices: %9.3f ms  %s\n",                                                \
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), msg);         \
-    }
     HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
     VERTEX_TRACE("begin")
-    hipStream_t s = c->stream;
     if (count) {
-        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + first_vertex, vertices, size_t(count) * sizeof(rayhip_vertex), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + first_vertex, vertices, size_t(count) * sizeof(rayhip_vertex), hipMemcpyHostToDevice, c->stream));
     }
     VERTEX_TRACE("vertices copied")
+    return refit_after_vertices(c, trace, t0);
+}
+
+// everything a vertex update recomputes once the new vertices are in c->vertices (in stream order behind them); `t0`: the start of
+// the call, for the stamps
+static int refit_after_vertices(rayhip_ctx *c, const bool trace, const std::chrono::steady_clock::time_point t0) {
+    rayhip_ctx::Refit &r = c->refit;
+    hipStream_t s = c->stream;
     const uint32_t n_tris = c->geometry.vtx_indices / 3;
     uint32_t *d_degenerate = r.scratch.as<uint32_t>();
     HIP_TRY(hipMemsetAsync(d_degenerate, 0, sizeof(uint32_t), s));
@@ -942,7 +979,6 @@ int rayhip_scene_update_vertices(rayhip_ctx *c, uint32_t first_vertex, uint32_t 
     }
     refresh_top_level_view(c, tlas_root, root_box, uint32_t(up.live.size()));
     VERTEX_TRACE("top level built")
-#undef VERTEX_TRACE
     return 0;
 }
 
@@ -961,6 +997,222 @@ int rayhip_scene_update_vertices_blob(rayhip_ctx *c, const void *blob, size_t si
     }
     return rayhip_scene_update_vertices(c, 0, d.vertices_count, d.vertices);
 }
+
+// ---- vertex updates whose vertices never pass through the host: skins, and arrays the caller holds on the device -------------------
+// Both run a kernel over the new vertices BEFORE the vertex array is written (posed into a staging array / checked where the caller has
+// them), read its counters back, and only then copy device to device and refit: a refused update has touched nothing.  skin.h, skin.hip.h.
+
+// 0 = the context can take a vertex update, 2 = it needs rayhip_scene_upload (the conditions of rayhip_scene_update_vertices)
+static int vertex_update_possible(rayhip_ctx *c, const char *who) {
+    if (!c->have_scene) {
+        (void)fail("%s before rayhip_scene_upload", who);
+        return 2;
+    }
+    if (c->wide == 8) {
+        (void)fail("%s: the context walks the 8-wide tree, whose builder runs on the host only", who);
+        return 2;
+    }
+    if (c->refit.levels_rc != 0 || c->refit.vertex_used.size() != c->geometry.vertices) {
+        (void)fail("%s: a bottom-level tree is higher than %u levels", who, rayhip_refit::MAX_LEVELS);
+        return 2;
+    }
+    return 0;
+}
+
+int rayhip_skin_create(rayhip_ctx *c, const rayhip_skin_desc *d, int *out_skin) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (!d || !out_skin || !d->bone_indices || !d->bone_weights) {
+        return fail("rayhip_skin_create: a null pointer");
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_skin_create")) {
+        return rc;
+    }
+    if (d->count == 0 || uint64_t(d->first_vertex) + d->count > c->geometry.vertices) {
+        return fail("rayhip_skin_create: vertices [%u, %u + %u) are outside the %u of the uploaded scene", d->first_vertex, d->first_vertex, d->count,
+                    c->geometry.vertices);
+    }
+    if (d->bones_count == 0 || d->bones_count > 65536u) {
+        return fail("rayhip_skin_create: %u bones (bone indices are 16-bit)", d->bones_count);
+    }
+    int slot = -1;
+    for (int k = int(rayhip_skin::MAX_SKINS) - 1; k >= 0; --k) {
+        const rayhip_ctx::Skin &o = c->skins[k];
+        if (!o.live) {
+            slot = k;
+        } else if (d->first_vertex < o.first + o.count && o.first < d->first_vertex + d->count) {
+            return fail("rayhip_skin_create: vertices [%u, %u + %u) overlap skin %d", d->first_vertex, d->first_vertex, d->count, o.id);
+        }
+    }
+    if (slot < 0) {
+        return fail("rayhip_skin_create: %u skins are live already", rayhip_skin::MAX_SKINS);
+    }
+    {
+        uint32_t where = 0;
+        if (const int bad = rayhip_skin::validate_influences(d->bone_indices, d->bone_weights, d->count, d->bones_count, where)) {
+            return bad == 1 ? fail("rayhip_skin_create: vertex %u names a bone outside the palette of %u", d->first_vertex + where, d->bones_count)
+                            : fail("rayhip_skin_create: a weight of vertex %u is negative or not finite", d->first_vertex + where);
+        }
+    }
+    for (const auto &kept : c->refit.light_vertices) {
+        if (kept.first >= d->first_vertex && kept.first - d->first_vertex < d->count) {
+            (void)fail("rayhip_skin_create: vertex %u belongs to a triangle light; lights are not rebuilt by a pose", kept.first);
+            return 2;
+        }
+    }
+    rayhip_ctx::Skin &k = c->skins[slot];
+    const size_t n = d->count;
+    if (k.rest.alloc(n * sizeof(rayhip_vertex)) || upload(c, k.indices, d->bone_indices, n * 4 * sizeof(uint16_t)) ||
+        upload(c, k.weights, d->bone_weights, n * 4 * sizeof(float))) {
+        return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(k.rest.p, d->rest ? static_cast<const void *>(d->rest) : static_cast<const void *>(c->vertices.as<rayhip_vertex>() + d->first_vertex),
+                           n * sizeof(rayhip_vertex), d->rest ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the caller's arrays may go away after this call
+    c->skin_serial = (c->skin_serial % 0x7ffffffu) + 1; // (1 .. 2^27 - 1: the handle stays a positive int, and is never a return code)
+    k.live = true, k.id = int(c->skin_serial << 4) | slot, k.first = d->first_vertex, k.count = d->count, k.bones_count = d->bones_count;
+    *out_skin = k.id;
+    return 0;
+}
+
+int rayhip_skin_destroy(rayhip_ctx *c, int skin) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (!c->skin_of(skin)) {
+        (void)fail("rayhip_skin_destroy: skin %d is not live", skin);
+        return 2;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rayhip_ctx::Skin &k = *c->skin_of(skin);
+    k.live = false;
+    k.rest.release(), k.indices.release(), k.weights.release();
+    return 0;
+}
+
+int rayhip_scene_pose_skins(rayhip_ctx *c, int n, const int *skins, const float *const *palettes) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (n < 0 || n > int(rayhip_skin::MAX_SKINS) || (n > 0 && (!skins || !palettes))) {
+        return fail("rayhip_scene_pose_skins: bad arguments");
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_scene_pose_skins")) {
+        return rc;
+    }
+    size_t stage_vertices = 0, palette_floats = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!c->skin_of(skins[i])) {
+            (void)fail("rayhip_scene_pose_skins: skin %d is not live", skins[i]);
+            return 2;
+        }
+        if (!palettes[i]) {
+            return fail("rayhip_scene_pose_skins: no palette for skin %d", skins[i]);
+        }
+        for (int j = 0; j < i; ++j) {
+            if (skins[j] == skins[i]) {
+                return fail("rayhip_scene_pose_skins: skin %d is named twice", skins[i]);
+            }
+        }
+        stage_vertices += c->skin_of(skins[i])->count, palette_floats += size_t(c->skin_of(skins[i])->bones_count) * 12;
+    }
+    if (n == 0) {
+        return 0;
+    }
+    const bool trace = getenv("RAYHIP_TRACE_UPLOAD") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    VERTEX_TRACE_AS("rayhip_scene_pose_skins", "begin")
+    hipStream_t s = c->stream;
+    if (c->skin_stage.alloc(stage_vertices * sizeof(rayhip_vertex)) || c->skin_palettes.alloc(palette_floats * sizeof(float)) ||
+        c->skin_counters.alloc(2 * sizeof(uint32_t))) {
+        return 1;
+    }
+    uint32_t *d_counters = c->skin_counters.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
+    {
+        size_t at_vertex = 0, at_float = 0;
+        for (int i = 0; i < n; ++i) {
+            const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
+            float *d_palette = c->skin_palettes.as<float>() + at_float;
+            HIP_TRY(hipMemcpyAsync(d_palette, palettes[i], size_t(k.bones_count) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+            rayhip_skin::k_skin_vertices<<<(k.count + 255) / 256, 256, 0, s>>>(k.rest.as<rayhip_vertex>(), k.indices.as<uint16_t>(), k.weights.as<float>(), k.count,
+                                                                              d_palette, k.bones_count, c->refit.d_vertex_used.as<uint8_t>() + k.first,
+                                                                              c->skin_stage.as<rayhip_vertex>() + at_vertex, d_counters);
+            HIP_TRY(hipGetLastError());
+            at_vertex += k.count, at_float += size_t(k.bones_count) * 12;
+        }
+    }
+    uint32_t counters[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (the caller's palettes may go away after this)
+    VERTEX_TRACE_AS("rayhip_scene_pose_skins", "vertices posed")
+    if (counters[0] != 0) {
+        return fail("rayhip_scene_pose_skins: the posed position of %u vertices is not finite", counters[0]);
+    }
+    {
+        size_t at_vertex = 0;
+        for (int i = 0; i < n; ++i) {
+            const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
+            HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + k.first, c->skin_stage.as<rayhip_vertex>() + at_vertex, size_t(k.count) * sizeof(rayhip_vertex),
+                                   hipMemcpyDeviceToDevice, s));
+            at_vertex += k.count;
+        }
+    }
+    VERTEX_TRACE_AS("rayhip_scene_pose_skins", "vertices copied")
+    return refit_after_vertices(c, trace, t0);
+}
+
+int rayhip_scene_update_vertices_device(rayhip_ctx *c, uint32_t first_vertex, uint32_t count, const rayhip_vertex *device_vertices) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_scene_update_vertices_device")) {
+        return rc;
+    }
+    if (uint64_t(first_vertex) + count > c->geometry.vertices || (count != 0 && device_vertices == nullptr)) {
+        return fail("rayhip_scene_update_vertices_device: vertices [%u, %u + %u) are outside the %u of the uploaded scene", first_vertex, first_vertex, count,
+                    c->geometry.vertices);
+    }
+    const bool trace = getenv("RAYHIP_TRACE_UPLOAD") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    VERTEX_TRACE_AS("rayhip_scene_update_vertices_device", "begin")
+    hipStream_t s = c->stream;
+    rayhip_ctx::Refit &r = c->refit;
+    if (c->skin_counters.alloc(2 * sizeof(uint32_t))) {
+        return 1;
+    }
+    uint32_t *d_counters = c->skin_counters.as<uint32_t>();
+    uint32_t counters[2] = {0, 0};
+    const uint32_t n_lights = uint32_t(r.light_vertices.size());
+    if (count) {
+        HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
+        rayhip_skin::k_check_vertices<<<(std::max(count, n_lights) + 255) / 256, 256, 0, s>>>(device_vertices, first_vertex, count, r.d_vertex_used.as<uint8_t>(),
+                                                                                             r.d_light_index.as<uint32_t>(), r.d_light_vertices.as<rayhip_vertex>(),
+                                                                                             n_lights, d_counters);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    VERTEX_TRACE_AS("rayhip_scene_update_vertices_device", "vertices checked")
+    if (counters[0] != 0) {
+        return fail("rayhip_scene_update_vertices_device: the position of %u vertices is not finite", counters[0]);
+    }
+    if (counters[1] != 0) {
+        (void)fail("rayhip_scene_update_vertices_device: %u vertices of triangle lights changed; lights are not rebuilt by this call", counters[1]);
+        return 2;
+    }
+    if (count) {
+        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + first_vertex, device_vertices, size_t(count) * sizeof(rayhip_vertex), hipMemcpyDeviceToDevice, s));
+    }
+    VERTEX_TRACE_AS("rayhip_scene_update_vertices_device", "vertices copied")
+    return refit_after_vertices(c, trace, t0);
+}
+
+#undef VERTEX_TRACE
+#undef VERTEX_TRACE_AS
 
 // test hook: a device array of the acceleration structure -> the host
 int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_bytes, size_t *out_bytes) {
@@ -1013,6 +1265,8 @@ int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_byt
         src = c->tris.p, bytes = size_t(c->refit.entries) * sizeof(rayhip_tri_accel);
     } else if (which == 2) {
         src = c->tri_indices.p, bytes = size_t(c->refit.entries) * sizeof(uint32_t);
+    } else if (which == 4) {
+        src = c->vertices.p, bytes = size_t(c->geometry.vertices) * sizeof(rayhip_vertex);
     } else {
         return fail("rayhip_k_read_accel: no array %d", which);
     }

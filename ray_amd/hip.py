@@ -75,6 +75,11 @@ class CacheGrid(C.Structure):  # rayhip_cache_grid == Ray::cache_grid_params_t
         return cls((C.c_float * 3)(*cam_pos), (C.c_float * 3)(*cam_pos_prev), 2.0, 50.0, exposure)
 
 
+class SkinDesc(C.Structure):  # rayhip_skin_desc
+    _fields_ = [("first_vertex", C.c_uint32), ("count", C.c_uint32), ("rest", C.c_void_p), ("bone_indices", C.c_void_p), ("bone_weights", C.c_void_p),
+                ("bones_count", C.c_uint32)]
+
+
 CACHE_ENTRIES = 1 << 22  # slots of the spatial cache's key table (rt_cache.h)
 # rayhip_cache_vertex: one vertex of a cache-update bounce
 CACHE_VERTEX_DTYPE = np.dtype([("o", "<f4", 3), ("t", "<f4"), ("d", "<f4", 3), ("path", "<u4"), ("n", "<f4", 3), ("ends", "<u4"),
@@ -93,7 +98,7 @@ assert VERTEX_DTYPE.itemsize == 44
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
@@ -193,6 +198,10 @@ class Library:
             f("scene_update_vertices").argtypes = [vp, u32, u32, vp]
             f("scene_update_vertices_blob").argtypes = [vp, vp, C.c_size_t]
             f("k_read_accel").argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+            f("scene_update_vertices_device").argtypes = [vp, u32, u32, vp]
+            f("skin_create").argtypes = [vp, C.POINTER(SkinDesc), C.POINTER(C.c_int)]
+            f("skin_destroy").argtypes = [vp, C.c_int]
+            f("scene_pose_skins").argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -309,15 +318,66 @@ class Context:
         self.L.check(rc)
         return 0
 
+    def update_vertices_device(self, first: int, count: int, device_pointer: int) -> int:
+        """new vertices [first, first + count) from `count` 44-byte records that are on this context's device already: `device_pointer`
+        is their address as an int (a tensor's data_ptr(), say), the data complete when the call is made
+        (rayhip_scene_update_vertices_device); returns as update_vertices()"""
+        rc = self.L.fn("scene_update_vertices_device")(self._ctx, int(first), int(count), C.c_void_p(int(device_pointer)))
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def create_skin(self, first: int, rest, indices: np.ndarray, weights: np.ndarray, bones_count: int) -> int:
+        """a skin over vertices [first, first + len(indices)) (rayhip_skin_create): `rest` VERTEX_DTYPE records or None (what the device
+        holds for the range now), `indices` [n][4] uint16, `weights` [n][4] float32.  Returns the skin's id (16 or more), or 2 where the ABI returns 2
+        (the context needs a full upload, or the range holds a vertex of a triangle light); an error raises."""
+        indices = np.ascontiguousarray(indices, dtype=np.uint16).reshape(-1, 4)
+        weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1, 4)
+        assert len(indices) == len(weights)
+        if rest is not None:
+            rest = np.ascontiguousarray(rest)
+            assert rest.dtype == VERTEX_DTYPE and len(rest) == len(indices)
+        d = SkinDesc(int(first), len(indices), rest.ctypes.data if rest is not None else None, indices.ctypes.data, weights.ctypes.data, int(bones_count))
+        out = C.c_int(-1)
+        rc = self.L.fn("skin_create")(self._ctx, C.byref(d), C.byref(out))
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return int(out.value)
+
+    def destroy_skin(self, skin: int) -> int:
+        rc = self.L.fn("skin_destroy")(self._ctx, int(skin))
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def pose_skins(self, palettes: dict) -> int:
+        """{skin id: palette [bones][3][4] float32}: every named skin posed from its rest pose and ONE refit (rayhip_scene_pose_skins);
+        returns as update_vertices()"""
+        ids = list(palettes)
+        arrays = [np.ascontiguousarray(palettes[k], dtype=np.float32) for k in ids]
+        assert all(a.ndim == 3 and a.shape[1:] == (3, 4) for a in arrays)
+        c_ids = (C.c_int * max(len(ids), 1))(*ids)
+        c_ptrs = (C.c_void_p * max(len(ids), 1))(*[a.ctypes.data for a in arrays])
+        rc = self.L.fn("scene_pose_skins")(self._ctx, len(ids), c_ids, c_ptrs)
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
     def read_accel(self, which: int) -> np.ndarray:
         """test hook (rayhip_k_read_accel): 0 the BVH2 nodes [n][16] u32 words, 1 the triangle records [n][12] f32, 2 tri_indices [n] u32,
-        3 the live top-level leaves [n][7] u32 words (instance slot, lo.xyz, hi.xyz as float bits), by slot"""
+        3 the live top-level leaves [n][7] u32 words (instance slot, lo.xyz, hi.xyz as float bits), by slot, 4 the vertex array as
+        VERTEX_DTYPE records"""
         n = C.c_size_t(0)
         self.L.fn("k_read_accel")(self._ctx, which, None, 0, C.byref(n))  # (refused: the size comes back)
         buf = np.zeros(max(int(n.value), 4) // 4, dtype=np.uint32)
         self.L.check(self.L.fn("k_read_accel")(self._ctx, which, buf.ctypes.data, buf.nbytes, C.byref(n)))
         buf = buf[:n.value // 4]
-        return {0: lambda: buf.reshape(-1, 16), 1: lambda: buf.view(np.float32).reshape(-1, 12), 2: lambda: buf, 3: lambda: buf.reshape(-1, 7)}[which]()
+        return {0: lambda: buf.reshape(-1, 16), 1: lambda: buf.view(np.float32).reshape(-1, 12), 2: lambda: buf, 3: lambda: buf.reshape(-1, 7),
+                4: lambda: buf.view(VERTEX_DTYPE)}[which]()
 
     def render(self, iteration: int, rect=None, cam: Camera = None, flags: int = 0, stats: Stats = None):
         rect = (0, 0, self.w, self.h) if rect is None else rect
