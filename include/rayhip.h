@@ -410,13 +410,13 @@ RAYHIP_API int rayhip_scene_update_instances_blob(rayhip_ctx *ctx, const void *b
  * [first, first+count) of the uploaded scene; topology unchanged.  Everything that depends on positions is recomputed on the
  * device (ray_amd/csrc/refit.h, refit.hip.h): the triangle records, the boxes of the bottom-level trees (refitted: the trees the
  * upload made are kept, all of them, whatever the range), the per-triangle vertex table, the 4-wide collapse, the instance boxes
- * and the top level (as rayhip_scene_update_instances rebuilds it).  Materials, lights, instances and textures stay.  The call
+ * and the top level (as rayhip_scene_update_instances rebuilds it).  Materials, lights (unless rayhip_scene_refit_lights is on), instances and textures stay.  The call
  * waits for the context's stream first and returns when the device work is done; the accumulated image is the caller's to
  * rayhip_clear.  Returns 0; 1 = error (a range outside the vertex array, a position of a vertex in use that is not finite -- both found before
  * anything is copied; after any other error re-send the scene with rayhip_scene_upload); 2 = needs rayhip_scene_upload, nothing
  * on the device was touched: no scene, a context that walks the 8-wide tree (its builder is host-only), a tree of more than 128
- * levels, or a CHANGED vertex of a triangle light (lights are not rebuilt; a vertex of a light's triangle that arrives bytewise
- * equal to what was uploaded is fine).  A triangle without area gets a record no ray can hit (their number goes into the
+ * levels, or a CHANGED vertex of a triangle light (lights are not rebuilt unless rayhip_scene_refit_lights is on; a vertex of a
+ * light's triangle that arrives bytewise equal to what was uploaded is fine).  A triangle without area gets a record no ray can hit (their number goes into the
  * RAYHIP_TRACE_UPLOAD trace; not an error); a triangle that had no area AT UPLOAD is not in the tree and stays absent, whatever
  * its corners become. */
 /* new positions / normals / bitangents / uvs for vertices [first, first+count) of the uploaded scene; topology unchanged */
@@ -426,8 +426,8 @@ RAYHIP_API int rayhip_scene_update_vertices_blob(rayhip_ctx *ctx, const void *bl
 /* The same update from vertices that are ALREADY ON THE DEVICE (the caller's own kernels, a tensor): `device_vertices` points at
  * `count` records in device memory of the context's device, complete when the call is made.  They are checked there (a kernel, two
  * counters read back), then copied device to device and refitted as above.  Returns as rayhip_scene_update_vertices: 1 for a range
- * outside the array or a position of a vertex in use that is not finite, 2 for a changed vertex of a triangle light -- both found
- * before the vertex array is written. */
+ * outside the array or a position of a vertex in use that is not finite, 2 for a changed vertex of a triangle light (lights are
+ * not rebuilt unless rayhip_scene_refit_lights is on) -- both found before the vertex array is written. */
 RAYHIP_API int rayhip_scene_update_vertices_device(rayhip_ctx *ctx, uint32_t first_vertex, uint32_t count, const rayhip_vertex *device_vertices);
 
 /* SKINS: the deformation itself on the device (ray_amd/csrc/skin.h, skin.hip.h).  A skin keeps the rest pose and the influences of
@@ -440,7 +440,8 @@ RAYHIP_API int rayhip_scene_update_vertices_device(rayhip_ctx *ctx, uint32_t fir
  * ranges; every rayhip_scene_upload[_blob] discards them all.  *out_skin is a handle of 16 or more -- never one of the return
  * codes -- and the handle of a destroyed or discarded skin names no later one.
  * Return values as rayhip_scene_update_vertices.  2 = needs rayhip_scene_upload, nothing touched: no scene, a skin id that is not
- * live, the 8-wide tree, a tree of more than 128 levels, or (at create time) a range that holds a vertex of a triangle light.
+ * live, the 8-wide tree, a tree of more than 128 levels, or (at create time) a range that holds a vertex of a triangle light
+ * (lights are not rebuilt unless rayhip_scene_refit_lights is on).
  * 1 = error: a range outside the array or overlapping a live skin, a bone index >= bones_count, a negative or non-finite weight,
  * a null pointer, a seventeenth skin, or a posed position of a vertex in use that is not finite (found before the vertex array is
  * written). */
@@ -455,9 +456,29 @@ RAYHIP_API int rayhip_skin_create(rayhip_ctx *ctx, const rayhip_skin_desc *desc,
 RAYHIP_API int rayhip_skin_destroy(rayhip_ctx *ctx, int skin);
 RAYHIP_API int rayhip_scene_pose_skins(rayhip_ctx *ctx, int n, const int *skins, const float *const *palettes); /* palettes[i]: bones_count x 12 */
 
+/* Emissive meshes that deform: 0 = off (default): unchanged behaviour.  1 = vertex updates and poses may move triangle lights.
+ * With the switch on, rayhip_scene_update_vertices[_blob|_device] accept changed vertices of triangle lights, rayhip_skin_create accepts
+ * ranges that hold such vertices, and every vertex update or pose refits ON THE DEVICE, behind the geometry and before it returns
+ * (ray_amd/csrc/light_refit.h, light_refit.hip.h): the world-space corners of the triangle lights, the 8-wide light tree (node boxes,
+ * quantised child boxes, flux, cone axis and cosines per child) and the per-node importance rows made from it.  The tree's TOPOLOGY
+ * is kept, as the vertex update keeps the BVH's: a refitted light tree samples worse the further the emitters move from their upload
+ * pose, and it is not the tree a fresh scene build would make -- flux and cones of inner nodes are folded over a node's children in
+ * slot order, the scene build's in the order of its binary tree, so inner fluxes differ in their last bits and inner cones slightly;
+ * both are valid trees.  The flux of an inner child keeps the ratio to the sum below it that the uploaded tree had (the scene build
+ * does not store the sum everywhere), so a refit at an unchanged pose gives the uploaded fluxes back.  A triangle light without area gets flux 0 and can never be picked (counted in the RAYHIP_TRACE_UPLOAD trace;
+ * not an error).  The refusals for the 8-wide tree, trees above 128 levels and positions that are not finite stay.
+ * The switch is a property of the context and survives uploads; it may be set before or after rayhip_scene_upload[_blob] -- whichever
+ * comes second prepares what the refit needs.  rayhip_scene_update_instances behaves as ever: the host's lights, light tree and
+ * vertices' kept copies replace the device's, and the host's tree describes the HOST's vertices -- a caller who deforms on the device
+ * poses or updates again after an instance update.  Returns 0; 1 = error, among them turning the switch off while a live skin covers
+ * a vertex of a triangle light (destroy the skin first).  After it is turned off, "changed" is judged against the vertices the
+ * lights on the device describe at that moment. */
+RAYHIP_API int rayhip_scene_refit_lights(rayhip_ctx *ctx, int on);
+
 /* test hook: copy a device array of the acceleration structure to the host. which: 0 BVH2 nodes [0, nodes_used),
  * 1 tris as 48-byte records (un-pitched), 2 tri_indices, 3 the live top-level leaves as (instance slot, lo.xyz, hi.xyz) 7 x 4 bytes each,
- * 4 the vertex array as 44-byte records */
+ * 4 the vertex array as 44-byte records, 5 the light tree (light_cwnodes, 208 bytes each), 6 its importance rows (light_children,
+ * 26 x 16 bytes per node), 7 the world-space corners of the triangle lights (light_tri_geom, 4 x 16 bytes per light slot) */
 RAYHIP_API int rayhip_k_read_accel(rayhip_ctx *ctx, int which, void *dst, size_t capacity_bytes, size_t *out_bytes);
 
 /* 1024-entry inverse filter CDF (RendererCPU.h:1234-1258 UpdateFilterTable; upload RendererVK.cpp:386-424) */

@@ -187,6 +187,19 @@ struct rayhip_ctx {
     DevBuf skin_stage;    // the posed vertices of one rayhip_scene_pose_skins call, skin after skin (sized to the largest call seen)
     DevBuf skin_palettes; // ... and its palettes
     DevBuf skin_counters; // [0] used vertices without a finite position, [1] changed light vertices
+    // rayhip_scene_refit_lights (light_refit.h): what a vertex update needs to refit the lights, prepared by whichever comes second of
+    // the switch and the upload, and again by an instance update
+    struct LightRefit {
+        bool on = false;                    // the switch: a property of the context, it survives uploads
+        bool ready = false;                 // the tables below describe the lights that are on the device
+        uint32_t lights_count = 0, li_count = 0, nodes_count = 0; // the light arrays on the device (upload_lights)
+        std::vector<uint32_t> level_offset; // level_nodes[level_offset[h] .. level_offset[h + 1]) are the tree's nodes of height h
+        DevBuf level_nodes;                 // the nodes of light_cwnodes sorted by height
+        DevBuf leaf;                        // one Summary per light slot: lights that are no triangles complete, triangles written by every refit
+        DevBuf node_summary;                // one Summary per node: scratch of the level launches
+        DevBuf slot_scale;                  // 8 floats per node: stored flux over summed flux of the inner slots at the upload pose (slot_scales)
+        uint32_t degenerate = 0;            // triangle lights without area the last refit met
+    } light_refit;
     void discard_skins() {
         for (Skin &k : skins) {
             k.live = false;
@@ -809,7 +822,8 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
     }
     c->stack_spill2.release();
     c->discard_skins();
-    for (DevBuf *b : {&c->skin_stage, &c->skin_palettes, &c->skin_counters, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices}) {
+    for (DevBuf *b : {&c->skin_stage, &c->skin_palettes, &c->skin_counters, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices,
+                      &c->light_refit.level_nodes, &c->light_refit.leaf, &c->light_refit.node_summary, &c->light_refit.slot_scale}) {
         b->release();
     }
     for (hipEvent_t e : c->events) {

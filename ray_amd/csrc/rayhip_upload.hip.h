@@ -98,7 +98,41 @@ int rayhip_bake_sky_blob(rayhip_ctx *c, const void *blob, size_t size, int w, in
     return rayhip_bake_sky(c, &d, w, h, out_rgbe8);
 }
 
+// ---- what a light refit needs of the lights that are on the device (rayhip_scene_refit_lights; light_refit.h) ------------------------
+// the tree's nodes sorted by height, the leaf summary table (lights that are no triangles complete: they do not move with vertices;
+// their flux from the tree as uploaded, since the environment light's needs the quadtree's mean luminance, which never reaches the
+// device), the flux scales of the inner slots (light_refit.h: slot_scales, one host refit at the pose the tree was built at) and the
+// scratch of the level launches.  `d`: the light arrays, vertices, indices and instances as they are on the device.
+static int prepare_light_refit(rayhip_ctx *c, const rayhip_scene_desc *d) {
+    const rayhip_light *lights = d->lights;
+    const rayhip_light_cwbvh_node *nodes = d->light_cwnodes;
+    const uint32_t n_lights = d->lights_count, n_nodes = d->light_cwnodes_count;
+    rayhip_ctx::LightRefit &lr = c->light_refit;
+    lr.ready = false;
+    std::vector<uint32_t> level_nodes;
+    if (const int rc = rayhip_light_refit::plan_levels(nodes, n_nodes, n_lights, level_nodes, lr.level_offset)) {
+        return rc == 2 ? fail("rayhip_scene_refit_lights: the light tree is higher than %u levels", rayhip_light_refit::MAX_LEVELS)
+                       : fail("rayhip_scene_refit_lights: a link of the light tree leaves its arrays, or a child lies before its parent");
+    }
+    const std::vector<rayhip_light_refit::Summary> leaf = rayhip_light_refit::leaf_table(lights, n_lights, nodes, n_nodes);
+    std::vector<float> scales;
+    if (rayhip_light_refit::slot_scales(lights, n_lights, d->li_indices, d->li_indices_count, d->mesh_instances, d->mesh_instances_count, d->vtx_indices,
+                                        d->vtx_indices_count, d->vertices, d->vertices_count, nodes, n_nodes, scales)) {
+        return fail("rayhip_scene_refit_lights: the light tree could not be refitted on the host");
+    }
+    if (upload(c, lr.slot_scale, scales.data(), scales.size() * sizeof(float)) || upload(c, lr.level_nodes, level_nodes.data(), level_nodes.size() * sizeof(uint32_t)) ||
+        upload(c, lr.leaf, leaf.data(), leaf.size() * sizeof(rayhip_light_refit::Summary)) ||
+        lr.node_summary.alloc(size_t(n_nodes) * sizeof(rayhip_light_refit::Summary))) {
+        return 1;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the three vectors go out of scope
+    lr.ready = true;
+    return 0;
+}
+
 static int upload_lights(rayhip_ctx *c, const rayhip_scene_desc *d) {
+    c->light_refit.ready = false;
+    c->light_refit.lights_count = d->lights_count, c->light_refit.li_count = d->li_indices_count, c->light_refit.nodes_count = d->light_cwnodes_count;
     if (upload(c, c->lights, d->lights, size_t(d->lights_count) * sizeof(*d->lights)) ||
         upload(c, c->li_indices, d->li_indices, size_t(d->li_indices_count) * sizeof(uint32_t)) ||
         upload(c, c->light_cwnodes, d->light_cwnodes, size_t(d->light_cwnodes_count) * sizeof(*d->light_cwnodes))) {
@@ -133,6 +167,9 @@ static int upload_lights(rayhip_ctx *c, const rayhip_scene_desc *d) {
         return 1;
     }
     HIP_TRY(hipStreamSynchronize(c->stream)); // `lc`, `tg` go out of scope
+    if (c->light_refit.on) {
+        return prepare_light_refit(c, d);
+    }
     return 0;
 }
 
@@ -831,6 +868,7 @@ int rayhip_scene_update_instances_blob(rayhip_ctx *c, const void *blob, size_t s
 #define VERTEX_TRACE(msg) VERTEX_TRACE_AS("rayhip_scene_update_vertices", msg)
 
 static int refit_after_vertices(rayhip_ctx *c, bool trace, std::chrono::steady_clock::time_point t0);
+static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, bool trace, std::chrono::steady_clock::time_point t0);
 
 // ---- vertex update: meshes deform in place, the trees are kept and refitted on the device ----------------------------------------
 // Kept: tree topology, triangle order (tri_indices), materials, lights, instances.  Recomputed from the new positions, all in stream
@@ -864,6 +902,9 @@ int rayhip_scene_update_vertices(rayhip_ctx *c, uint32_t first_vertex, uint32_t 
         }
     }
     for (const auto &kept : r.light_vertices) { // (ascending; few)
+        if (c->light_refit.on) {
+            break; // (rayhip_scene_refit_lights: the lights follow their vertices)
+        }
         if (kept.first >= first_vertex && kept.first - first_vertex < count &&
             memcmp(&vertices[kept.first - first_vertex], &kept.second, sizeof(rayhip_vertex)) != 0) {
             (void)fail("rayhip_scene_update_vertices: vertex %u belongs to a triangle light; lights are not rebuilt by this call", kept.first);
@@ -888,7 +929,7 @@ static int refit_after_vertices(rayhip_ctx *c, const bool trace, const std::chro
     hipStream_t s = c->stream;
     const uint32_t n_tris = c->geometry.vtx_indices / 3;
     uint32_t *d_degenerate = r.scratch.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(d_degenerate, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(d_degenerate, 0, 2 * sizeof(uint32_t), s)); // ([1]: triangle LIGHTS without area, when the lights are refitted)
     if (r.entries) {
         rayhip_refit::k_refit_tris<<<(r.entries + 255) / 256, 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(),
                                                                            n_tris, c->tri_indices.as<uint32_t>(), r.first_entry.as<uint32_t>(), r.entries,
@@ -910,6 +951,12 @@ static int refit_after_vertices(rayhip_ctx *c, const bool trace, const std::chro
         HIP_TRY(hipGetLastError());
     }
     VERTEX_TRACE("tri_verts done")
+    if (c->light_refit.on) { // rayhip_scene_refit_lights: the lights follow the vertices just written
+        if (refit_lights(c, d_degenerate + 1, trace, t0)) {
+            return 1;
+        }
+        HIP_TRY(hipMemcpyAsync(&c->light_refit.degenerate, d_degenerate + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
     // the root node of every mesh in use -> the host; the count of triangles without area comes with them
     std::vector<rayhip_bvh2_node> root_nodes(r.roots.size());
     {
@@ -945,6 +992,9 @@ static int refit_after_vertices(rayhip_ctx *c, const bool trace, const std::chro
     VERTEX_TRACE(c->wide == 4 ? "bvh4 built" : "no wide BLAS")
     if (trace) {
         fprintf(stderr, "rayhip_scene_update_vertices: %u triangles without area\n", r.degenerate);
+        if (c->light_refit.on) {
+            fprintf(stderr, "rayhip_scene_update_vertices: %u triangle lights without area\n", c->light_refit.degenerate);
+        }
     }
     // the top level over the new instance boxes: the live slots and the instance array of the last upload / instance update.  The leaf
     // numbering is the one scene_update.h: plan documents (a leaf names the slot the host's leaf named); the box of a slot is made from
@@ -979,6 +1029,83 @@ static int refit_after_vertices(rayhip_ctx *c, const bool trace, const std::chro
     }
     refresh_top_level_view(c, tlas_root, root_box, uint32_t(up.live.size()));
     VERTEX_TRACE("top level built")
+    return 0;
+}
+
+// ---- the switch: vertex updates and poses may move triangle lights (light_refit.h) --------------------------------------------------
+// A property of the context.  Whichever comes second of this call and the upload prepares the tables (prepare_light_refit): here from
+// the light arrays read back, which hold the topology and the fluxes of the lights that are no triangles whatever refits ran before.
+int rayhip_scene_refit_lights(rayhip_ctx *c, int on) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    rayhip_ctx::LightRefit &lr = c->light_refit;
+    if (!on) {
+        if (!lr.on) {
+            return 0;
+        }
+        for (const rayhip_ctx::Skin &k : c->skins) {
+            for (const auto &kept : c->refit.light_vertices) {
+                if (k.live && kept.first >= k.first && kept.first - k.first < k.count) {
+                    return fail("rayhip_scene_refit_lights: skin %d covers vertex %u of a triangle light; destroy it first", k.id, kept.first);
+                }
+            }
+        }
+        // from here on a changed light vertex is refused again: "changed" against what the lights on the device describe NOW
+        if (c->have_scene && !c->refit.light_vertices.empty()) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            std::vector<rayhip_vertex> now(c->geometry.vertices);
+            HIP_TRY(hipMemcpy(now.data(), c->vertices.p, now.size() * sizeof(rayhip_vertex), hipMemcpyDeviceToHost));
+            for (auto &kept : c->refit.light_vertices) {
+                if (kept.first < now.size()) {
+                    kept.second = now[kept.first];
+                }
+            }
+            if (upload_vertex_checks(c, false)) {
+                return 1;
+            }
+        }
+        lr.on = false;
+        return 0;
+    }
+    if (lr.on) {
+        return 0;
+    }
+    if (c->have_scene && !lr.ready) {
+        // everything the tables are made from, read back: the tree is the one the last upload or instance update brought (no refit ran
+        // since: the switch was off).  The pose it describes is that of the KEPT light vertices -- taken from the host's arrays with the
+        // tree, re-taken from the device when the switch went off, and unchangeable while it is off -- not necessarily what the vertex
+        // array holds: an instance update that came while the switch was off left a deformed emitter where it was
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        std::vector<rayhip_light> lights(lr.lights_count);
+        std::vector<rayhip_light_cwbvh_node> nodes(lr.nodes_count);
+        std::vector<uint32_t> li(lr.li_count), vi(c->geometry.vtx_indices);
+        std::vector<rayhip_vertex> vertices(c->geometry.vertices);
+        std::vector<rayhip_mesh_instance> instances(c->instances_count);
+        auto back = [&](void *dst, const DevBuf &src, const size_t bytes) {
+            return bytes == 0 || hipMemcpy(dst, src.p, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+        };
+        if (!back(lights.data(), c->lights, lights.size() * sizeof(rayhip_light)) || !back(nodes.data(), c->light_cwnodes, nodes.size() * sizeof(rayhip_light_cwbvh_node)) ||
+            !back(li.data(), c->li_indices, li.size() * sizeof(uint32_t)) || !back(vi.data(), c->vtx_indices, vi.size() * sizeof(uint32_t)) ||
+            !back(vertices.data(), c->vertices, vertices.size() * sizeof(rayhip_vertex)) ||
+            !back(instances.data(), c->mesh_instances, instances.size() * sizeof(rayhip_mesh_instance))) {
+            return fail("rayhip_scene_refit_lights: reading the scene back failed");
+        }
+        for (const auto &kept : c->refit.light_vertices) {
+            if (kept.first < vertices.size()) {
+                vertices[kept.first] = kept.second;
+            }
+        }
+        rayhip_scene_desc d = {};
+        d.lights = lights.data(), d.lights_count = lr.lights_count, d.light_cwnodes = nodes.data(), d.light_cwnodes_count = lr.nodes_count;
+        d.li_indices = li.data(), d.li_indices_count = lr.li_count, d.vtx_indices = vi.data(), d.vtx_indices_count = uint32_t(vi.size());
+        d.vertices = vertices.data(), d.vertices_count = uint32_t(vertices.size());
+        d.mesh_instances = instances.data(), d.mesh_instances_count = uint32_t(instances.size());
+        if (prepare_light_refit(c, &d)) {
+            return 1;
+        }
+    }
+    lr.on = true;
     return 0;
 }
 
@@ -1019,6 +1146,37 @@ static int vertex_update_possible(rayhip_ctx *c, const char *who) {
     return 0;
 }
 
+// the light refit behind the geometry refit of a vertex update, in stream order (light_refit.hip.h): the triangle lights' corners
+// and summaries, then the tree, one launch per height.  `d_degenerate`: where the triangles without area are counted.
+static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, const bool trace, const std::chrono::steady_clock::time_point t0) {
+    rayhip_ctx::LightRefit &lr = c->light_refit;
+    if (!lr.ready) {
+        return fail("rayhip_scene_refit_lights is on, but its tables are not prepared");
+    }
+    hipStream_t s = c->stream;
+    if (lr.li_count) {
+        rayhip_light_refit::k_refit_tri_lights<<<(lr.li_count + 255) / 256, 256, 0, s>>>(
+            c->lights.as<rayhip_light>(), lr.lights_count, c->li_indices.as<uint32_t>(), lr.li_count, c->mesh_instances.as<rayhip_mesh_instance>(), c->instances_count,
+            c->vtx_indices.as<uint32_t>(), c->geometry.vtx_indices, c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->light_tri_geom.as<float4>(),
+            lr.leaf.as<rayhip_light_refit::Summary>(), d_degenerate);
+        HIP_TRY(hipGetLastError());
+    }
+    VERTEX_TRACE("light corners")
+    for (size_t h = 0; h + 1 < lr.level_offset.size(); ++h) {
+        const uint32_t n = lr.level_offset[h + 1] - lr.level_offset[h];
+        if (n == 0) {
+            continue;
+        }
+        rayhip_light_refit::k_refit_light_level<<<unsigned((size_t(n) * 8 + 255) / 256), 256, 0, s>>>(
+            c->light_cwnodes.as<rayhip_light_cwbvh_node>(), lr.level_nodes.as<uint32_t>() + lr.level_offset[h], n, c->lights.as<rayhip_light>(),
+            lr.leaf.as<rayhip_light_refit::Summary>(), lr.node_summary.as<rayhip_light_refit::Summary>(), c->light_children.as<float4>(),
+            lr.slot_scale.as<float>());
+        HIP_TRY(hipGetLastError());
+    }
+    VERTEX_TRACE("light tree refitted")
+    return 0;
+}
+
 int rayhip_skin_create(rayhip_ctx *c, const rayhip_skin_desc *d, int *out_skin) {
     if (!c || use_device(c)) {
         return 1;
@@ -1056,6 +1214,9 @@ int rayhip_skin_create(rayhip_ctx *c, const rayhip_skin_desc *d, int *out_skin) 
         }
     }
     for (const auto &kept : c->refit.light_vertices) {
+        if (c->light_refit.on) {
+            break; // (rayhip_scene_refit_lights: the lights follow their vertices)
+        }
         if (kept.first >= d->first_vertex && kept.first - d->first_vertex < d->count) {
             (void)fail("rayhip_skin_create: vertex %u belongs to a triangle light; lights are not rebuilt by a pose", kept.first);
             return 2;
@@ -1186,7 +1347,7 @@ int rayhip_scene_update_vertices_device(rayhip_ctx *c, uint32_t first_vertex, ui
     }
     uint32_t *d_counters = c->skin_counters.as<uint32_t>();
     uint32_t counters[2] = {0, 0};
-    const uint32_t n_lights = uint32_t(r.light_vertices.size());
+    const uint32_t n_lights = c->light_refit.on ? 0u : uint32_t(r.light_vertices.size()); // (refitted lights may move: nothing to compare)
     if (count) {
         HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
         rayhip_skin::k_check_vertices<<<(std::max(count, n_lights) + 255) / 256, 256, 0, s>>>(device_vertices, first_vertex, count, r.d_vertex_used.as<uint8_t>(),
@@ -1267,6 +1428,12 @@ int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_byt
         src = c->tri_indices.p, bytes = size_t(c->refit.entries) * sizeof(uint32_t);
     } else if (which == 4) {
         src = c->vertices.p, bytes = size_t(c->geometry.vertices) * sizeof(rayhip_vertex);
+    } else if (which == 5) {
+        src = c->light_cwnodes.p, bytes = size_t(c->light_refit.nodes_count) * sizeof(rayhip_light_cwbvh_node);
+    } else if (which == 6) {
+        src = c->light_children.p, bytes = size_t(c->light_refit.nodes_count) * LIGHT_CHILDREN_STRIDE * sizeof(float4);
+    } else if (which == 7) {
+        src = c->light_tri_geom.p, bytes = size_t(c->light_refit.lights_count) * 4 * sizeof(float4);
     } else {
         return fail("rayhip_k_read_accel: no array %d", which);
     }

@@ -94,11 +94,15 @@ HIT_DTYPE = np.dtype([("obj_index", "<i4"), ("prim_index", "<i4"), ("t", "<f4"),
 assert RAY_DTYPE.itemsize == 72 and SHADOW_RAY_DTYPE.itemsize == 48 and HIT_DTYPE.itemsize == 20
 VERTEX_DTYPE = np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("b", "<f4", 3), ("t", "<f4", 2)])  # rayhip_vertex
 assert VERTEX_DTYPE.itemsize == 44
+LIGHT_NODE_DTYPE = np.dtype([("bbox_min", "<f4", 3), ("_unused0", "<f4"), ("bbox_max", "<f4", 3), ("_unused1", "<f4"), ("ch_bbox_min", "u1", (3, 8)),
+                             ("ch_bbox_max", "u1", (3, 8)), ("child", "<u4", 8), ("flux", "<f4", 8), ("axis", "<u4", 8),
+                             ("cos_omega_ne", "<u4", 8)])  # rayhip_light_cwbvh_node
+assert LIGHT_NODE_DTYPE.itemsize == 208
 
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "scene_refit_lights", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
@@ -202,6 +206,7 @@ class Library:
             f("skin_create").argtypes = [vp, C.POINTER(SkinDesc), C.POINTER(C.c_int)]
             f("skin_destroy").argtypes = [vp, C.c_int]
             f("scene_pose_skins").argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
+            f("scene_refit_lights").argtypes = [vp, C.c_int]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -367,17 +372,26 @@ class Context:
         self.L.check(rc)
         return 0
 
+    def refit_lights(self, on: bool) -> int:
+        """the switch rayhip_scene_refit_lights: with it on, vertex updates and poses may move the vertices of triangle lights -- their
+        corners, the light tree and its importance rows are refitted on the device behind the geometry.  Returns 0; turning it off under
+        a live skin that covers a vertex of a triangle light raises."""
+        self.L.check(self.L.fn("scene_refit_lights")(self._ctx, 1 if on else 0))
+        return 0
+
     def read_accel(self, which: int) -> np.ndarray:
         """test hook (rayhip_k_read_accel): 0 the BVH2 nodes [n][16] u32 words, 1 the triangle records [n][12] f32, 2 tri_indices [n] u32,
         3 the live top-level leaves [n][7] u32 words (instance slot, lo.xyz, hi.xyz as float bits), by slot, 4 the vertex array as
-        VERTEX_DTYPE records"""
+        VERTEX_DTYPE records, 5 the light tree as LIGHT_NODE_DTYPE records (208 bytes each), 6 its importance rows [nodes][26][4] f32,
+        7 the world-space corners of the triangle lights [light slots][4][4] f32"""
         n = C.c_size_t(0)
         self.L.fn("k_read_accel")(self._ctx, which, None, 0, C.byref(n))  # (refused: the size comes back)
         buf = np.zeros(max(int(n.value), 4) // 4, dtype=np.uint32)
         self.L.check(self.L.fn("k_read_accel")(self._ctx, which, buf.ctypes.data, buf.nbytes, C.byref(n)))
         buf = buf[:n.value // 4]
         return {0: lambda: buf.reshape(-1, 16), 1: lambda: buf.view(np.float32).reshape(-1, 12), 2: lambda: buf, 3: lambda: buf.reshape(-1, 7),
-                4: lambda: buf.view(VERTEX_DTYPE)}[which]()
+                4: lambda: buf.view(VERTEX_DTYPE), 5: lambda: buf.view(LIGHT_NODE_DTYPE), 6: lambda: buf.view(np.float32).reshape(-1, 26, 4),
+                7: lambda: buf.view(np.float32).reshape(-1, 4, 4)}[which]()
 
     def render(self, iteration: int, rect=None, cam: Camera = None, flags: int = 0, stats: Stats = None):
         rect = (0, 0, self.w, self.h) if rect is None else rect
