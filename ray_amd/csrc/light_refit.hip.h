@@ -1,4 +1,4 @@
-// light_refit.hip.h -- the device side of the light refit (rayhip_scene_refit_lights; refit_after_vertices in rayhip_upload.hip.h): the
+// light_refit.hip.h -- the device side of the light refit (rayhip_scene_refit_lights; refit_after_vertices in rayhip_deform.hip.h): the
 // element functions of light_refit.h.  The tree is refitted with ONE LAUNCH PER HEIGHT, lowest first, as refit.hip.h refits the BVH:
 // a launch reads the summaries the launches before it wrote, and the kernel boundary is what makes them visible -- no flags between
 // waves.  Within a launch EIGHT LANES share a node, one per child slot (eight nodes per wavefront): the box union and the fold in

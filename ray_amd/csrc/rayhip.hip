@@ -42,6 +42,7 @@ using namespace rt;
 
 // the host side, in parts (one translation unit with the kernels above: templates and launch sites see each other)
 #include "rayhip_ctx.hip.h"
+#include "rayhip_deform.hip.h"
 #include "rayhip_upload.hip.h"
 #include "rayhip_render.hip.h"
 #include "rayhip_denoise.hip.h"

@@ -152,6 +152,8 @@ struct rayhip_ctx {
     uint32_t tex_table[8] = {}, textures_count = 0, tex_flags = 0;
     struct { uint32_t vertices, vtx_indices, tri_materials, materials; } geometry = {};
     uint32_t instances_count = 0; // mesh instances on the device (scene_upload and scene_update set it)
+    // ---- deforming the scene that is on the device (rayhip_deform.hip.h): the tables an upload or instance update leaves for a vertex
+    // update, the same for the light refit behind it, and the skins.  rayhip_ctx_destroy releases what lies here in one list.
     // what rayhip_scene_update_vertices needs of the last full upload / instance update (refit.h)
     struct Refit {
         DevBuf level_nodes;                 // bottom-level BVH2 nodes sorted by height ...
@@ -171,22 +173,6 @@ struct rayhip_ctx {
         DevBuf d_vertex_used;                     // vertex_used
         DevBuf d_light_index, d_light_vertices;   // light_vertices as two arrays
     } refit;
-    // skins (rayhip_skin_create, skin.h): rest pose and influences of a vertex range, on the device until the next scene upload
-    struct Skin {
-        bool live = false;
-        int id = 0; // the handle the caller holds: (serial << 4) | slot, so a handle of a discarded skin never names a later one
-        uint32_t first = 0, count = 0, bones_count = 0;
-        DevBuf rest, indices, weights; // rayhip_vertex [count], uint16 [count][4], float [count][4]
-    } skins[rayhip_skin::MAX_SKINS];
-    uint32_t skin_serial = 0;
-    // the live skin handle `id` names, or null
-    Skin *skin_of(const int id) {
-        Skin &k = skins[id & int(rayhip_skin::MAX_SKINS - 1)];
-        return id > 0 && k.live && k.id == id ? &k : nullptr;
-    }
-    DevBuf skin_stage;    // the posed vertices of one rayhip_scene_pose_skins call, skin after skin (sized to the largest call seen)
-    DevBuf skin_palettes; // ... and its palettes
-    DevBuf skin_counters; // [0] used vertices without a finite position, [1] changed light vertices
     // rayhip_scene_refit_lights (light_refit.h): what a vertex update needs to refit the lights, prepared by whichever comes second of
     // the switch and the upload, and again by an instance update
     struct LightRefit {
@@ -200,12 +186,29 @@ struct rayhip_ctx {
         DevBuf slot_scale;                  // 8 floats per node: stored flux over summed flux of the inner slots at the upload pose (slot_scales)
         uint32_t degenerate = 0;            // triangle lights without area the last refit met
     } light_refit;
+    // skins (rayhip_skin_create, skin.h): rest pose and influences of a vertex range, on the device until the next scene upload
+    struct Skin {
+        bool live = false;
+        int id = 0; // the handle the caller holds: (serial << 4) | slot, so a handle of a discarded skin never names a later one
+        uint32_t first = 0, count = 0, bones_count = 0;
+        DevBuf rest, indices, weights; // rayhip_vertex [count], uint16 [count][4], float [count][4]
+    } skins[rayhip_skin::MAX_SKINS];
+    uint32_t skin_serial = 0;
+    // the live skin handle `id` names, or null
+    Skin *skin_of(const int id) {
+        Skin &k = skins[id & int(rayhip_skin::MAX_SKINS - 1)];
+        return id > 0 && k.live && k.id == id ? &k : nullptr;
+    }
     void discard_skins() {
         for (Skin &k : skins) {
             k.live = false;
             k.rest.release(), k.indices.release(), k.weights.release();
         }
     }
+    DevBuf skin_stage;    // the posed vertices of one rayhip_scene_pose_skins call, skin after skin (sized to the largest call seen)
+    DevBuf skin_palettes; // ... and its palettes
+    DevBuf skin_counters; // [0] used vertices without a finite position, [1] changed light vertices
+    // ---- (deforming: end) ----
     bool adaptive_dirty = false; // a pass ran with variance_threshold != 0 since the last Clear / Resize: required_samples may
                                  // lie below the next iteration, so passes are not batched (rayhip_render_batch)
     int lut_transform = 0, lut_dims = 0;
@@ -822,8 +825,9 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
     }
     c->stack_spill2.release();
     c->discard_skins();
-    for (DevBuf *b : {&c->skin_stage, &c->skin_palettes, &c->skin_counters, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices,
-                      &c->light_refit.level_nodes, &c->light_refit.leaf, &c->light_refit.node_summary, &c->light_refit.slot_scale}) {
+    for (DevBuf *b : {&c->refit.level_nodes, &c->refit.first_entry, &c->refit.scratch, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices,
+                      &c->light_refit.level_nodes, &c->light_refit.leaf, &c->light_refit.node_summary, &c->light_refit.slot_scale, &c->skin_stage,
+                      &c->skin_palettes, &c->skin_counters}) {
         b->release();
     }
     for (hipEvent_t e : c->events) {

@@ -1,0 +1,659 @@
+// rayhip_deform.hip.h -- part of librayhip's host side (one translation unit: included by rayhip.hip before rayhip_upload.hip.h):
+// deforming a scene that is on the device.  In reading order: the tables an upload or instance update leaves behind (prepare_refit,
+// keep_light_vertices, upload_vertex_checks, prepare_light_refit), the phase stamps, the preconditions, the light refit and the
+// geometry refit behind new vertices, the entry points (rayhip_scene_update_vertices, its _blob and _device forms; refit.h), the
+// skins (rayhip_skin_create / _destroy, rayhip_scene_pose_skins; skin.h) and the switch (rayhip_scene_refit_lights; light_refit.h).
+#pragma once
+
+// what the refit needs of the upload's half of the launcher (rayhip_upload.hip.h)
+static int rebuild_top_level(rayhip_ctx *c, const rayhip_update::Plan &up, uint32_t &tlas_root, rayhip_lbvh::Box &root_box);
+static void refresh_top_level_view(rayhip_ctx *c, uint32_t tlas_root, const rayhip_lbvh::Box &root_box, uint32_t live_instances);
+
+// ---- what a later rayhip_scene_update_vertices needs of an upload (refit.h) -----------------------------------------------------
+// the bottom-level nodes sorted by height and the first entry of every triangle, on the device; the root list of the collapse; the
+// live instances and the instance array on the host.  `nodes` / `instances` / `tri_indices`: the arrays as uploaded.
+static int prepare_refit(rayhip_ctx *c, const rayhip_bvh2_node *nodes, const uint32_t nodes_count, const rayhip_mesh_instance *instances,
+                         const uint32_t instances_count, const uint32_t tlas_root, const uint32_t *tri_indices, const uint32_t entries,
+                         const uint32_t *vtx_indices, const uint32_t n_tris, const uint32_t n_vertices, const bool rebased_for_bvh8) {
+    rayhip_ctx::Refit &r = c->refit;
+    r.level_offset.clear(), r.roots.clear(), r.ordinal_of_root.clear(), r.live.clear();
+    r.levels_rc = 2, r.entries = entries, r.degenerate = 0;
+    // the vertices some triangle of the table uses: the vertex array is a sparse pool, a free slot may hold anything
+    r.vertex_used.assign(n_vertices, 0);
+    for (uint32_t e = 0; e < entries; ++e) {
+        for (uint32_t k = 0; tri_indices[e] < n_tris && k < 3; ++k) {
+            const uint32_t v = vtx_indices[size_t(tri_indices[e]) * 3 + k];
+            if (v < n_vertices) {
+                r.vertex_used[v] = 1;
+            }
+        }
+    }
+    r.instances.assign(instances, instances + instances_count);
+    std::vector<std::pair<uint32_t, uint32_t>> top;
+    if (tlas_root != 0xffffffffu && rayhip_rebuild::collect_leaf_ranges(nodes, nodes_count, tlas_root, top)) {
+        for (const auto &leaf : top) {
+            r.live.push_back(leaf.first);
+        }
+        std::sort(r.live.begin(), r.live.end());
+        r.live.erase(std::unique(r.live.begin(), r.live.end()), r.live.end());
+    }
+    if (rebased_for_bvh8) {
+        return 0; // (the 8-wide builder is host-only: such a context refuses the vertex update)
+    }
+    std::vector<uint32_t> root_of_instance;
+    if (!rayhip_bvh4::collect_roots(nodes, nodes_count, instances, instances_count, tlas_root, r.roots, root_of_instance)) {
+        r.roots.clear();
+    }
+    for (size_t k = 0; k < r.roots.size(); ++k) {
+        r.ordinal_of_root[r.roots[k]] = uint32_t(k);
+    }
+    std::vector<uint32_t> level_nodes;
+    r.levels_rc = rayhip_refit::plan_levels(nodes, nodes_count, r.roots, level_nodes, r.level_offset);
+    if (r.levels_rc != 0) {
+        return 0; // (a tree above 128 levels: the update says so when it is asked for)
+    }
+    const std::vector<uint32_t> first = rayhip_refit::first_entries(tri_indices, entries, n_tris);
+    if (upload(c, r.level_nodes, level_nodes.data(), level_nodes.size() * sizeof(uint32_t)) ||
+        upload(c, r.first_entry, first.data(), first.size() * sizeof(uint32_t)) ||
+        r.scratch.alloc(256 + r.roots.size() * (sizeof(uint32_t) + sizeof(rayhip_bvh2_node)) + 64)) {
+        return 1;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the two vectors go out of scope
+    return 0;
+}
+
+// the vertices some triangle light's triangle uses, as they are on the device: the light arrays are not rebuilt by a vertex update,
+// so it refuses to move one of these
+static void keep_light_vertices(rayhip_ctx *c, const rayhip_scene_desc *d) {
+    std::vector<std::pair<uint32_t, rayhip_vertex>> &kept = c->refit.light_vertices;
+    kept.clear();
+    for (uint32_t k = 0; k < d->li_indices_count; ++k) {
+        const uint32_t i = d->li_indices[k];
+        if (i >= d->lights_count || light_type(d->lights[i]) != LIGHT_TYPE_TRI) {
+            continue;
+        }
+        const size_t tri = float_as_uint(d->lights[i].params[0]);
+        for (size_t j = tri * 3; j < tri * 3 + 3 && j < d->vtx_indices_count; ++j) {
+            if (d->vtx_indices[j] < d->vertices_count) {
+                kept.emplace_back(d->vtx_indices[j], d->vertices[d->vtx_indices[j]]);
+            }
+        }
+    }
+    std::sort(kept.begin(), kept.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+    kept.erase(std::unique(kept.begin(), kept.end(), [](const auto &x, const auto &y) { return x.first == y.first; }), kept.end());
+}
+
+// ... and on the device, with the per-vertex `used` flags, for the updates whose vertices never pass through the host
+// (k_skin_vertices, k_check_vertices: skin.hip.h).  `with_used`: the flags too (they change with an upload only).
+static int upload_vertex_checks(rayhip_ctx *c, const bool with_used) {
+    rayhip_ctx::Refit &r = c->refit;
+    std::vector<uint32_t> index(r.light_vertices.size());
+    std::vector<rayhip_vertex> kept(r.light_vertices.size());
+    for (size_t k = 0; k < r.light_vertices.size(); ++k) {
+        index[k] = r.light_vertices[k].first, kept[k] = r.light_vertices[k].second;
+    }
+    if (upload(c, r.d_light_index, index.data(), index.size() * sizeof(uint32_t)) ||
+        upload(c, r.d_light_vertices, kept.data(), kept.size() * sizeof(rayhip_vertex)) ||
+        (with_used && upload(c, r.d_vertex_used, r.vertex_used.data(), r.vertex_used.size()))) {
+        return 1;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the two vectors go out of scope
+    return 0;
+}
+
+// ---- what a light refit needs of the lights that are on the device (rayhip_scene_refit_lights; light_refit.h) ------------------------
+// the tree's nodes sorted by height, the leaf summary table (lights that are no triangles complete: they do not move with vertices;
+// their flux from the tree as uploaded, since the environment light's needs the quadtree's mean luminance, which never reaches the
+// device), the flux scales of the inner slots (light_refit.h: slot_scales, one host refit at the pose the tree was built at) and the
+// scratch of the level launches.  `d`: the light arrays, vertices, indices and instances as they are on the device.
+static int prepare_light_refit(rayhip_ctx *c, const rayhip_scene_desc *d) {
+    const rayhip_light *lights = d->lights;
+    const rayhip_light_cwbvh_node *nodes = d->light_cwnodes;
+    const uint32_t n_lights = d->lights_count, n_nodes = d->light_cwnodes_count;
+    rayhip_ctx::LightRefit &lr = c->light_refit;
+    lr.ready = false;
+    std::vector<uint32_t> level_nodes;
+    if (const int rc = rayhip_light_refit::plan_levels(nodes, n_nodes, n_lights, level_nodes, lr.level_offset)) {
+        return rc == 2 ? fail("rayhip_scene_refit_lights: the light tree is higher than %u levels", rayhip_light_refit::MAX_LEVELS)
+                       : fail("rayhip_scene_refit_lights: a link of the light tree leaves its arrays, or a child lies before its parent");
+    }
+    const std::vector<rayhip_light_refit::Summary> leaf = rayhip_light_refit::leaf_table(lights, n_lights, nodes, n_nodes);
+    std::vector<float> scales;
+    if (rayhip_light_refit::slot_scales(lights, n_lights, d->li_indices, d->li_indices_count, d->mesh_instances, d->mesh_instances_count, d->vtx_indices,
+                                        d->vtx_indices_count, d->vertices, d->vertices_count, nodes, n_nodes, scales)) {
+        return fail("rayhip_scene_refit_lights: the light tree could not be refitted on the host");
+    }
+    if (upload(c, lr.slot_scale, scales.data(), scales.size() * sizeof(float)) || upload(c, lr.level_nodes, level_nodes.data(), level_nodes.size() * sizeof(uint32_t)) ||
+        upload(c, lr.leaf, leaf.data(), leaf.size() * sizeof(rayhip_light_refit::Summary)) ||
+        lr.node_summary.alloc(size_t(n_nodes) * sizeof(rayhip_light_refit::Summary))) {
+        return 1;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the three vectors go out of scope
+    lr.ready = true;
+    return 0;
+}
+
+// ---- the phase stamps of a vertex update (RAYHIP_TRACE_UPLOAD) ------------------------------------------------------------------------
+// A stamp waits for the device first, so that the phases can be told apart -- only when tracing.  `who`: the entry point the line names.
+struct VertexStamps {
+    rayhip_ctx *c;
+    const char *who;
+    bool on = getenv("RAYHIP_TRACE_UPLOAD") != nullptr;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(); // the start of the call
+    hipError_t stamp(const char *msg) const {
+        const hipError_t e = on ? hipStreamSynchronize(c->stream) : hipSuccess;
+        if (on && e == hipSuccess) {
+            fprintf(stderr, "%s: %9.3f ms  %s\n", who, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), msg);
+        }
+        return e;
+    }
+};
+
+// ---- the preconditions every entry point shares ------------------------------------------------------------------------------------------
+// 0 = the context can take a vertex update, 2 = it needs rayhip_scene_upload
+static int vertex_update_possible(rayhip_ctx *c, const char *who) {
+    if (!c->have_scene) {
+        (void)fail("%s before rayhip_scene_upload", who);
+        return 2;
+    }
+    if (c->wide == 8) {
+        (void)fail("%s: the context walks the 8-wide tree, whose builder runs on the host only", who);
+        return 2;
+    }
+    // (vertex_used: prepare_refit assigns one flag per vertex, so after a successful upload the sizes agree; only an upload that
+    // failed after it, over a scene that was there, leaves them apart -- and the checks below index the flags by the scene's count)
+    if (c->refit.levels_rc != 0 || c->refit.vertex_used.size() != c->geometry.vertices) {
+        (void)fail("%s: a bottom-level tree is higher than %u levels", who, rayhip_refit::MAX_LEVELS);
+        return 2;
+    }
+    return 0;
+}
+
+static int outside_the_scene(const rayhip_ctx *c, const char *who, const uint32_t first, const uint32_t count) {
+    return fail("%s: vertices [%u, %u + %u) are outside the %u of the uploaded scene", who, first, first, count, c->geometry.vertices);
+}
+
+// Light vertices are pinned unless the switch is on (rayhip_scene_refit_lights: the lights follow their vertices).  The lowest vertex of
+// [first, first + count) that a triangle light uses and that would move, or null: `vertices` are the new ones, of which a bytewise
+// unchanged one passes; without them every light vertex of the range counts.  (The device form: k_check_vertices, skin.hip.h.)
+static const uint32_t *pinned_light_vertex(const rayhip_ctx *c, const uint32_t first, const uint32_t count, const rayhip_vertex *vertices) {
+    if (c->light_refit.on) {
+        return nullptr;
+    }
+    for (const auto &kept : c->refit.light_vertices) { // (ascending; few)
+        if (kept.first >= first && kept.first - first < count &&
+            (!vertices || memcmp(&vertices[kept.first - first], &kept.second, sizeof(rayhip_vertex)) != 0)) {
+            return &kept.first;
+        }
+    }
+    return nullptr;
+}
+
+// ---- the light refit behind the geometry refit of a vertex update, in stream order (light_refit.hip.h) ------------------------------
+// the triangle lights' corners and summaries, then the tree, one launch per height.  `d_degenerate`: where the triangles without area
+// are counted.
+static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, const VertexStamps &st) {
+    rayhip_ctx::LightRefit &lr = c->light_refit;
+    if (!lr.ready) {
+        return fail("rayhip_scene_refit_lights is on, but its tables are not prepared");
+    }
+    hipStream_t s = c->stream;
+    if (lr.li_count) {
+        rayhip_light_refit::k_refit_tri_lights<<<(lr.li_count + 255) / 256, 256, 0, s>>>(
+            c->lights.as<rayhip_light>(), lr.lights_count, c->li_indices.as<uint32_t>(), lr.li_count, c->mesh_instances.as<rayhip_mesh_instance>(), c->instances_count,
+            c->vtx_indices.as<uint32_t>(), c->geometry.vtx_indices, c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->light_tri_geom.as<float4>(),
+            lr.leaf.as<rayhip_light_refit::Summary>(), d_degenerate);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(st.stamp("light corners"));
+    for (size_t h = 0; h + 1 < lr.level_offset.size(); ++h) {
+        const uint32_t n = lr.level_offset[h + 1] - lr.level_offset[h];
+        if (n == 0) {
+            continue;
+        }
+        rayhip_light_refit::k_refit_light_level<<<unsigned((size_t(n) * 8 + 255) / 256), 256, 0, s>>>(
+            c->light_cwnodes.as<rayhip_light_cwbvh_node>(), lr.level_nodes.as<uint32_t>() + lr.level_offset[h], n, c->lights.as<rayhip_light>(),
+            lr.leaf.as<rayhip_light_refit::Summary>(), lr.node_summary.as<rayhip_light_refit::Summary>(), c->light_children.as<float4>(),
+            lr.slot_scale.as<float>());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(st.stamp("light tree refitted"));
+    return 0;
+}
+
+// ---- vertex update: meshes deform in place, the trees are kept and refitted on the device ----------------------------------------
+// Kept: tree topology, triangle order (tri_indices), materials, lights, instances.  Recomputed from the new positions, all in stream
+// order: the triangle records (k_refit_tris), the child boxes of every bottom-level BVH2 node (k_refit_level, one launch per height),
+// the per-triangle vertex table (k_fill_tri_verts), the 4-wide collapse over the same root list, the instance boxes (host, from the root
+// nodes read back) and the top level (the path of rayhip_scene_update_instances).  refit.h / refit.hip.h.
+
+// everything a vertex update recomputes once the new vertices are in c->vertices (in stream order behind them).  `st`: the caller's
+// stamps, for the start of the call; the lines written from here name rayhip_scene_update_vertices whichever entry point called
+// (tools/vertex_update_bench.py reads the phases by that prefix)
+static int refit_after_vertices(rayhip_ctx *c, VertexStamps st) {
+    st.who = "rayhip_scene_update_vertices";
+    rayhip_ctx::Refit &r = c->refit;
+    hipStream_t s = c->stream;
+    const uint32_t n_tris = c->geometry.vtx_indices / 3;
+    uint32_t *d_degenerate = r.scratch.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(d_degenerate, 0, 2 * sizeof(uint32_t), s)); // ([1]: triangle LIGHTS without area, when the lights are refitted)
+    if (r.entries) {
+        rayhip_refit::k_refit_tris<<<(r.entries + 255) / 256, 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(),
+                                                                           n_tris, c->tri_indices.as<uint32_t>(), r.first_entry.as<uint32_t>(), r.entries,
+                                                                           c->tris.as<float4>(), c->tri_pitch, d_degenerate);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(st.stamp("triangle records"));
+    for (size_t h = 1; h < r.level_offset.size(); ++h) {
+        const uint32_t n = r.level_offset[h] - r.level_offset[h - 1];
+        rayhip_refit::k_refit_level<<<(n + 255) / 256, 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), r.level_nodes.as<uint32_t>() + r.level_offset[h - 1], n,
+                                                                    c->tri_indices.as<uint32_t>(), c->vtx_indices.as<uint32_t>(), c->vertices.as<rayhip_vertex>());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(st.stamp("boxes refitted"));
+    if (n_tris) {
+        k_fill_tri_verts<<<(n_tris + 255) / 256, 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(), n_tris,
+                                                              c->tri_materials.as<rayhip_tri_mat_data>(), c->geometry.tri_materials, c->tri_verts.as<float4>(),
+                                                              c->tri_bitangents.as<float4>());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(st.stamp("tri_verts done"));
+    if (c->light_refit.on) { // rayhip_scene_refit_lights: the lights follow the vertices just written
+        if (refit_lights(c, d_degenerate + 1, st)) {
+            return 1;
+        }
+        HIP_TRY(hipMemcpyAsync(&c->light_refit.degenerate, d_degenerate + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    // the root node of every mesh in use -> the host; the count of triangles without area comes with them
+    std::vector<rayhip_bvh2_node> root_nodes(r.roots.size());
+    {
+        uint32_t *d_which = reinterpret_cast<uint32_t *>(r.scratch.as<uint8_t>() + 256);
+        rayhip_bvh2_node *d_roots = reinterpret_cast<rayhip_bvh2_node *>(r.scratch.as<uint8_t>() + 256 + ((r.roots.size() * sizeof(uint32_t) + 63) & ~size_t(63)));
+        if (!r.roots.empty()) {
+            HIP_TRY(hipMemcpyAsync(d_which, r.roots.data(), r.roots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            rayhip_refit::k_gather_nodes<<<unsigned((r.roots.size() + 255) / 256), 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), d_which, uint32_t(r.roots.size()),
+                                                                                               d_roots);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(root_nodes.data(), d_roots, r.roots.size() * sizeof(rayhip_bvh2_node), hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipMemcpyAsync(&r.degenerate, d_degenerate, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    // the 4-wide trees over the boxes just written: the same root list as at upload, so the wide node of roots[k] is k again
+    if (c->wide == 4 && !r.roots.empty()) {
+        uint32_t n_wide = 0;
+        std::string why;
+        bool unquantisable = false;
+        if (!rayhip_bvh4::build_device(s, c->nodes.as<rayhip_bvh2_node>(), c->nodes_used, r.roots, c->nodes4.as<Bvh4Node>(), n_wide, why, &unquantisable)) {
+            if (!unquantisable) {
+                return fail("4-wide collapse failed: %s", why.c_str());
+            }
+            // a box the grid cannot hold: the kernels walk the BVH2 from here on, as after an upload of such a scene
+            c->wide = 0, c->small_scene = false;
+            c->sc.nodes4 = nullptr, c->sc.blas_root4 = nullptr;
+            for (auto &ref : c->mesh_refs) {
+                ref.second.root4 = 0;
+            }
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(st.stamp(c->wide == 4 ? "bvh4 built" : "no wide BLAS"));
+    if (st.on) {
+        fprintf(stderr, "rayhip_scene_update_vertices: %u triangles without area\n", r.degenerate);
+        if (c->light_refit.on) {
+            fprintf(stderr, "rayhip_scene_update_vertices: %u triangle lights without area\n", c->light_refit.degenerate);
+        }
+    }
+    // the top level over the new instance boxes: the live slots and the instance array of the last upload / instance update.  The leaf
+    // numbering is the one scene_update.h: plan documents (a leaf names the slot the host's leaf named); the box of a slot is made from
+    // that slot's own mesh and transform, which is what the walk follows the leaf to.
+    rayhip_update::Plan up;
+    up.live = r.live, up.instances = r.instances;
+    up.root4.assign(up.instances.size(), 0u);
+    for (const uint32_t mi : up.live) {
+        const auto it = mi < up.instances.size() ? r.ordinal_of_root.find(up.instances[mi].node_index) : r.ordinal_of_root.end();
+        if (it == r.ordinal_of_root.end()) {
+            return fail("rayhip_scene_update_vertices: instance %u has no tree on the device", mi);
+        }
+        up.root4[mi] = c->wide == 4 ? it->second : 0u;
+        up.boxes.push_back(rayhip_rebuild::transform_box(rayhip_rebuild::node_box(root_nodes[it->second]), up.instances[mi].xform));
+    }
+    if (c->wide == 4) {
+        for (auto &ref : c->mesh_refs) {
+            const auto it = r.ordinal_of_root.find(ref.second.node_index);
+            if (it != r.ordinal_of_root.end()) {
+                ref.second.root4 = it->second;
+            }
+        }
+        if (upload(c, c->blas_root4, up.root4.data(), up.root4.size() * sizeof(uint32_t))) {
+            return 1;
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    uint32_t tlas_root = 0xffffffffu;
+    rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
+    if (const int rc = rebuild_top_level(c, up, tlas_root, root_box)) {
+        return rc == 2 ? fail("rayhip_scene_update_vertices: %s", g_err.c_str()) : rc; // (the arrays are the new ones already: an error)
+    }
+    refresh_top_level_view(c, tlas_root, root_box, uint32_t(up.live.size()));
+    HIP_TRY(st.stamp("top level built"));
+    return 0;
+}
+
+// ---- the entry points ----------------------------------------------------------------------------------------------------------------------
+// vertices from the host: checked here, in loops, before anything is copied
+int rayhip_scene_update_vertices(rayhip_ctx *c, uint32_t first_vertex, uint32_t count, const rayhip_vertex *vertices) {
+    if (use_device(c)) {
+        return 1;
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_scene_update_vertices")) {
+        return rc;
+    }
+    if (uint64_t(first_vertex) + count > c->geometry.vertices || (count != 0 && vertices == nullptr)) {
+        return outside_the_scene(c, "rayhip_scene_update_vertices", first_vertex, count);
+    }
+    for (uint32_t i = 0; i < count; ++i) {
+        if (c->refit.vertex_used[first_vertex + i] &&
+            (!std::isfinite(vertices[i].p[0]) || !std::isfinite(vertices[i].p[1]) || !std::isfinite(vertices[i].p[2]))) {
+            return fail("rayhip_scene_update_vertices: the position of vertex %u is not finite", first_vertex + i);
+        }
+    }
+    if (const uint32_t *pinned = pinned_light_vertex(c, first_vertex, count, vertices)) {
+        (void)fail("rayhip_scene_update_vertices: vertex %u belongs to a triangle light; lights are not rebuilt by this call", *pinned);
+        return 2;
+    }
+    const VertexStamps st{c, "rayhip_scene_update_vertices"};
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    if (count) {
+        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + first_vertex, vertices, size_t(count) * sizeof(rayhip_vertex), hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(st.stamp("vertices copied"));
+    return refit_after_vertices(c, st);
+}
+
+int rayhip_scene_update_vertices_blob(rayhip_ctx *c, const void *blob, size_t size) {
+    rayhip_scene_desc d;
+    rayhip_camera cam;
+    const float *ft = nullptr;
+    int ftn = 0;
+    std::string err;
+    if (!rayhip_blob::deserialize(blob, size, d, cam, &ft, &ftn, err, nullptr)) {
+        return fail("%s", err.c_str());
+    }
+    if (c && c->have_scene && (d.vertices_count != c->geometry.vertices || d.vtx_indices_count != c->geometry.vtx_indices)) {
+        return fail("rayhip_scene_update_vertices_blob: the blob holds %u vertices / %u indices, the uploaded scene %u / %u", d.vertices_count,
+                    d.vtx_indices_count, c->geometry.vertices, c->geometry.vtx_indices);
+    }
+    return rayhip_scene_update_vertices(c, 0, d.vertices_count, d.vertices);
+}
+
+// ---- vertex updates whose vertices never pass through the host: arrays the caller holds on the device, and skins ------------------
+// Both run a kernel over the new vertices BEFORE the vertex array is written (checked where the caller has them / posed into a staging
+// array), read its counters back, and only then copy device to device and refit: a refused update has touched nothing.  skin.h,
+// skin.hip.h.  (The two flows are kept apart: they share the order of their steps but no step -- one kernel or one per skin, one
+// counter judged or two, one copy or one per skin -- so a common helper would take each step as a callback and shorten neither.)
+int rayhip_scene_update_vertices_device(rayhip_ctx *c, uint32_t first_vertex, uint32_t count, const rayhip_vertex *device_vertices) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_scene_update_vertices_device")) {
+        return rc;
+    }
+    if (uint64_t(first_vertex) + count > c->geometry.vertices || (count != 0 && device_vertices == nullptr)) {
+        return outside_the_scene(c, "rayhip_scene_update_vertices_device", first_vertex, count);
+    }
+    const VertexStamps st{c, "rayhip_scene_update_vertices_device"};
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    hipStream_t s = c->stream;
+    rayhip_ctx::Refit &r = c->refit;
+    if (c->skin_counters.alloc(2 * sizeof(uint32_t))) {
+        return 1;
+    }
+    uint32_t *d_counters = c->skin_counters.as<uint32_t>();
+    uint32_t counters[2] = {0, 0};
+    const uint32_t n_lights = c->light_refit.on ? 0u : uint32_t(r.light_vertices.size()); // (refitted lights may move: nothing to compare)
+    if (count) {
+        HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
+        rayhip_skin::k_check_vertices<<<(std::max(count, n_lights) + 255) / 256, 256, 0, s>>>(device_vertices, first_vertex, count, r.d_vertex_used.as<uint8_t>(),
+                                                                                             r.d_light_index.as<uint32_t>(), r.d_light_vertices.as<rayhip_vertex>(),
+                                                                                             n_lights, d_counters);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    HIP_TRY(st.stamp("vertices checked"));
+    if (counters[0] != 0) {
+        return fail("rayhip_scene_update_vertices_device: the position of %u vertices is not finite", counters[0]);
+    }
+    if (counters[1] != 0) {
+        (void)fail("rayhip_scene_update_vertices_device: %u vertices of triangle lights changed; lights are not rebuilt by this call", counters[1]);
+        return 2;
+    }
+    // (the counters are back and zero: from here on the live vertex array is written)
+    if (count) {
+        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + first_vertex, device_vertices, size_t(count) * sizeof(rayhip_vertex), hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(st.stamp("vertices copied"));
+    return refit_after_vertices(c, st);
+}
+
+// ---- the skins ---------------------------------------------------------------------------------------------------------------------------
+int rayhip_skin_create(rayhip_ctx *c, const rayhip_skin_desc *d, int *out_skin) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (!d || !out_skin || !d->bone_indices || !d->bone_weights) {
+        return fail("rayhip_skin_create: a null pointer");
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_skin_create")) {
+        return rc;
+    }
+    if (d->count == 0 || uint64_t(d->first_vertex) + d->count > c->geometry.vertices) {
+        return outside_the_scene(c, "rayhip_skin_create", d->first_vertex, d->count);
+    }
+    if (d->bones_count == 0 || d->bones_count > 65536u) {
+        return fail("rayhip_skin_create: %u bones (bone indices are 16-bit)", d->bones_count);
+    }
+    int slot = -1;
+    for (int k = int(rayhip_skin::MAX_SKINS) - 1; k >= 0; --k) {
+        const rayhip_ctx::Skin &o = c->skins[k];
+        if (!o.live) {
+            slot = k;
+        } else if (d->first_vertex < o.first + o.count && o.first < d->first_vertex + d->count) {
+            return fail("rayhip_skin_create: vertices [%u, %u + %u) overlap skin %d", d->first_vertex, d->first_vertex, d->count, o.id);
+        }
+    }
+    if (slot < 0) {
+        return fail("rayhip_skin_create: %u skins are live already", rayhip_skin::MAX_SKINS);
+    }
+    {
+        uint32_t where = 0;
+        if (const int bad = rayhip_skin::validate_influences(d->bone_indices, d->bone_weights, d->count, d->bones_count, where)) {
+            return bad == 1 ? fail("rayhip_skin_create: vertex %u names a bone outside the palette of %u", d->first_vertex + where, d->bones_count)
+                            : fail("rayhip_skin_create: a weight of vertex %u is negative or not finite", d->first_vertex + where);
+        }
+    }
+    if (const uint32_t *pinned = pinned_light_vertex(c, d->first_vertex, d->count, nullptr)) { // (a pose may put it anywhere)
+        (void)fail("rayhip_skin_create: vertex %u belongs to a triangle light; lights are not rebuilt by a pose", *pinned);
+        return 2;
+    }
+    rayhip_ctx::Skin &k = c->skins[slot];
+    const size_t n = d->count;
+    if (k.rest.alloc(n * sizeof(rayhip_vertex)) || upload(c, k.indices, d->bone_indices, n * 4 * sizeof(uint16_t)) ||
+        upload(c, k.weights, d->bone_weights, n * 4 * sizeof(float))) {
+        return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(k.rest.p, d->rest ? static_cast<const void *>(d->rest) : static_cast<const void *>(c->vertices.as<rayhip_vertex>() + d->first_vertex),
+                           n * sizeof(rayhip_vertex), d->rest ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the caller's arrays may go away after this call
+    c->skin_serial = (c->skin_serial % 0x7ffffffu) + 1; // (1 .. 2^27 - 1: the handle stays a positive int, and is never a return code)
+    k.live = true, k.id = int(c->skin_serial << 4) | slot, k.first = d->first_vertex, k.count = d->count, k.bones_count = d->bones_count;
+    *out_skin = k.id;
+    return 0;
+}
+
+int rayhip_skin_destroy(rayhip_ctx *c, int skin) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (!c->skin_of(skin)) {
+        (void)fail("rayhip_skin_destroy: skin %d is not live", skin);
+        return 2;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rayhip_ctx::Skin &k = *c->skin_of(skin);
+    k.live = false;
+    k.rest.release(), k.indices.release(), k.weights.release();
+    return 0;
+}
+
+int rayhip_scene_pose_skins(rayhip_ctx *c, int n, const int *skins, const float *const *palettes) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (n < 0 || n > int(rayhip_skin::MAX_SKINS) || (n > 0 && (!skins || !palettes))) {
+        return fail("rayhip_scene_pose_skins: bad arguments");
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_scene_pose_skins")) {
+        return rc;
+    }
+    size_t stage_vertices = 0, palette_floats = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!c->skin_of(skins[i])) {
+            (void)fail("rayhip_scene_pose_skins: skin %d is not live", skins[i]);
+            return 2;
+        }
+        if (!palettes[i]) {
+            return fail("rayhip_scene_pose_skins: no palette for skin %d", skins[i]);
+        }
+        for (int j = 0; j < i; ++j) {
+            if (skins[j] == skins[i]) {
+                return fail("rayhip_scene_pose_skins: skin %d is named twice", skins[i]);
+            }
+        }
+        stage_vertices += c->skin_of(skins[i])->count, palette_floats += size_t(c->skin_of(skins[i])->bones_count) * 12;
+    }
+    if (n == 0) {
+        return 0;
+    }
+    const VertexStamps st{c, "rayhip_scene_pose_skins"};
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    hipStream_t s = c->stream;
+    if (c->skin_stage.alloc(stage_vertices * sizeof(rayhip_vertex)) || c->skin_palettes.alloc(palette_floats * sizeof(float)) ||
+        c->skin_counters.alloc(2 * sizeof(uint32_t))) {
+        return 1;
+    }
+    uint32_t *d_counters = c->skin_counters.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
+    {
+        size_t at_vertex = 0, at_float = 0;
+        for (int i = 0; i < n; ++i) {
+            const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
+            float *d_palette = c->skin_palettes.as<float>() + at_float;
+            HIP_TRY(hipMemcpyAsync(d_palette, palettes[i], size_t(k.bones_count) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+            rayhip_skin::k_skin_vertices<<<(k.count + 255) / 256, 256, 0, s>>>(k.rest.as<rayhip_vertex>(), k.indices.as<uint16_t>(), k.weights.as<float>(), k.count,
+                                                                              d_palette, k.bones_count, c->refit.d_vertex_used.as<uint8_t>() + k.first,
+                                                                              c->skin_stage.as<rayhip_vertex>() + at_vertex, d_counters);
+            HIP_TRY(hipGetLastError());
+            at_vertex += k.count, at_float += size_t(k.bones_count) * 12;
+        }
+    }
+    uint32_t counters[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (the caller's palettes may go away after this)
+    HIP_TRY(st.stamp("vertices posed"));
+    if (counters[0] != 0) {
+        return fail("rayhip_scene_pose_skins: the posed position of %u vertices is not finite", counters[0]);
+    }
+    // (the counter is back and zero: from here on the live vertex array is written)
+    {
+        size_t at_vertex = 0;
+        for (int i = 0; i < n; ++i) {
+            const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
+            HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + k.first, c->skin_stage.as<rayhip_vertex>() + at_vertex, size_t(k.count) * sizeof(rayhip_vertex),
+                                   hipMemcpyDeviceToDevice, s));
+            at_vertex += k.count;
+        }
+    }
+    HIP_TRY(st.stamp("vertices copied"));
+    return refit_after_vertices(c, st);
+}
+
+// ---- the switch: vertex updates and poses may move triangle lights (light_refit.h) --------------------------------------------------
+// A property of the context.  Whichever comes second of this call and the upload prepares the tables (prepare_light_refit): here from
+// the light arrays read back, which hold the topology and the fluxes of the lights that are no triangles whatever refits ran before.
+int rayhip_scene_refit_lights(rayhip_ctx *c, int on) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    rayhip_ctx::LightRefit &lr = c->light_refit;
+    if (!on) {
+        if (!lr.on) {
+            return 0;
+        }
+        for (const rayhip_ctx::Skin &k : c->skins) {
+            for (const auto &kept : c->refit.light_vertices) {
+                if (k.live && kept.first >= k.first && kept.first - k.first < k.count) {
+                    return fail("rayhip_scene_refit_lights: skin %d covers vertex %u of a triangle light; destroy it first", k.id, kept.first);
+                }
+            }
+        }
+        // from here on a changed light vertex is refused again: "changed" against what the lights on the device describe NOW
+        if (c->have_scene && !c->refit.light_vertices.empty()) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            std::vector<rayhip_vertex> now(c->geometry.vertices);
+            HIP_TRY(hipMemcpy(now.data(), c->vertices.p, now.size() * sizeof(rayhip_vertex), hipMemcpyDeviceToHost));
+            for (auto &kept : c->refit.light_vertices) {
+                if (kept.first < now.size()) {
+                    kept.second = now[kept.first];
+                }
+            }
+            if (upload_vertex_checks(c, false)) {
+                return 1;
+            }
+        }
+        lr.on = false;
+        return 0;
+    }
+    if (lr.on) {
+        return 0;
+    }
+    if (c->have_scene && !lr.ready) {
+        // everything the tables are made from, read back: the tree is the one the last upload or instance update brought (no refit ran
+        // since: the switch was off).  The pose it describes is that of the KEPT light vertices -- taken from the host's arrays with the
+        // tree, re-taken from the device when the switch went off, and unchangeable while it is off -- not necessarily what the vertex
+        // array holds: an instance update that came while the switch was off left a deformed emitter where it was
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        std::vector<rayhip_light> lights(lr.lights_count);
+        std::vector<rayhip_light_cwbvh_node> nodes(lr.nodes_count);
+        std::vector<uint32_t> li(lr.li_count), vi(c->geometry.vtx_indices);
+        std::vector<rayhip_vertex> vertices(c->geometry.vertices);
+        std::vector<rayhip_mesh_instance> instances(c->instances_count);
+        auto back = [&](void *dst, const DevBuf &src, const size_t bytes) {
+            return bytes == 0 || hipMemcpy(dst, src.p, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+        };
+        if (!back(lights.data(), c->lights, lights.size() * sizeof(rayhip_light)) || !back(nodes.data(), c->light_cwnodes, nodes.size() * sizeof(rayhip_light_cwbvh_node)) ||
+            !back(li.data(), c->li_indices, li.size() * sizeof(uint32_t)) || !back(vi.data(), c->vtx_indices, vi.size() * sizeof(uint32_t)) ||
+            !back(vertices.data(), c->vertices, vertices.size() * sizeof(rayhip_vertex)) ||
+            !back(instances.data(), c->mesh_instances, instances.size() * sizeof(rayhip_mesh_instance))) {
+            return fail("rayhip_scene_refit_lights: reading the scene back failed");
+        }
+        for (const auto &kept : c->refit.light_vertices) {
+            if (kept.first < vertices.size()) {
+                vertices[kept.first] = kept.second;
+            }
+        }
+        rayhip_scene_desc d = {};
+        d.lights = lights.data(), d.lights_count = lr.lights_count, d.light_cwnodes = nodes.data(), d.light_cwnodes_count = lr.nodes_count;
+        d.li_indices = li.data(), d.li_indices_count = lr.li_count, d.vtx_indices = vi.data(), d.vtx_indices_count = uint32_t(vi.size());
+        d.vertices = vertices.data(), d.vertices_count = uint32_t(vertices.size());
+        d.mesh_instances = instances.data(), d.mesh_instances_count = uint32_t(instances.size());
+        if (prepare_light_refit(c, &d)) {
+            return 1;
+        }
+    }
+    lr.on = true;
+    return 0;
+}

@@ -1,8 +1,8 @@
 // rayhip_upload.hip.h -- part of librayhip's host side (one translation unit: included by rayhip.hip, in this order, after the kernels):
-// scene upload: lights and derived tables, the scene view, rayhip_scene_upload (validation, leaf refinement, wide collapse),
-// rayhip_scene_update_instances (top level rebuilt on the device), rayhip_scene_update_vertices (records, boxes, collapse and top level
-// recomputed on the device under the kept trees; refit.h) and its siblings that never see the vertices on the host (rayhip_skin_create /
-// rayhip_scene_pose_skins, rayhip_scene_update_vertices_device; skin.h), filter table, tonemap LUT, the blob forms, the hook rayhip_k_read_accel.
+// getting a scene onto the device: the sky, lights and their derived tables, the scene view, the top level rebuilt on the device,
+// rayhip_scene_upload (validation, then its phases: leaf refinement, layout, bottom level and wide collapse, shading arrays, lights,
+// textures), rayhip_scene_update_instances, filter table, tonemap LUT, the blob forms, the hook rayhip_k_read_accel.  What deforms a
+// scene that is there (vertex updates, skins, the light refit) and the tables an upload leaves for it: rayhip_deform.hip.h.
 #pragma once
 
 // the physical sky (rayhip_sky + its tables and textures: 1.6 MB): device copies and the view the kernels read; the directional-light
@@ -31,8 +31,6 @@ static int upload_sky(rayhip_ctx *c, const rayhip_scene_desc *d) {
     return 0;
 }
 
-// lights, their index list, the light tree (+ its per-node importance table) and the world-space corners of the triangle
-// lights: everything an instance / light change replaces besides the top-level tree
 // The sky environment map baked ON THE DEVICE (round 5; VERDICT round 4, missing 5): what Scene::PrepareSkyEnvMap produces on the host
 // (SceneCPU.cpp:1017-1056 over CalcSkyEnvTexture, SceneCommon.cpp:286-361) and the reference's GPU scene in a compute pass (SceneGPU.h:1697-1768).
 // Takes the sky part of a scene description (sky, its two tables, its five textures, sky_dir_lights) and the light array; writes w x h RGBE8 texels
@@ -98,38 +96,8 @@ int rayhip_bake_sky_blob(rayhip_ctx *c, const void *blob, size_t size, int w, in
     return rayhip_bake_sky(c, &d, w, h, out_rgbe8);
 }
 
-// ---- what a light refit needs of the lights that are on the device (rayhip_scene_refit_lights; light_refit.h) ------------------------
-// the tree's nodes sorted by height, the leaf summary table (lights that are no triangles complete: they do not move with vertices;
-// their flux from the tree as uploaded, since the environment light's needs the quadtree's mean luminance, which never reaches the
-// device), the flux scales of the inner slots (light_refit.h: slot_scales, one host refit at the pose the tree was built at) and the
-// scratch of the level launches.  `d`: the light arrays, vertices, indices and instances as they are on the device.
-static int prepare_light_refit(rayhip_ctx *c, const rayhip_scene_desc *d) {
-    const rayhip_light *lights = d->lights;
-    const rayhip_light_cwbvh_node *nodes = d->light_cwnodes;
-    const uint32_t n_lights = d->lights_count, n_nodes = d->light_cwnodes_count;
-    rayhip_ctx::LightRefit &lr = c->light_refit;
-    lr.ready = false;
-    std::vector<uint32_t> level_nodes;
-    if (const int rc = rayhip_light_refit::plan_levels(nodes, n_nodes, n_lights, level_nodes, lr.level_offset)) {
-        return rc == 2 ? fail("rayhip_scene_refit_lights: the light tree is higher than %u levels", rayhip_light_refit::MAX_LEVELS)
-                       : fail("rayhip_scene_refit_lights: a link of the light tree leaves its arrays, or a child lies before its parent");
-    }
-    const std::vector<rayhip_light_refit::Summary> leaf = rayhip_light_refit::leaf_table(lights, n_lights, nodes, n_nodes);
-    std::vector<float> scales;
-    if (rayhip_light_refit::slot_scales(lights, n_lights, d->li_indices, d->li_indices_count, d->mesh_instances, d->mesh_instances_count, d->vtx_indices,
-                                        d->vtx_indices_count, d->vertices, d->vertices_count, nodes, n_nodes, scales)) {
-        return fail("rayhip_scene_refit_lights: the light tree could not be refitted on the host");
-    }
-    if (upload(c, lr.slot_scale, scales.data(), scales.size() * sizeof(float)) || upload(c, lr.level_nodes, level_nodes.data(), level_nodes.size() * sizeof(uint32_t)) ||
-        upload(c, lr.leaf, leaf.data(), leaf.size() * sizeof(rayhip_light_refit::Summary)) ||
-        lr.node_summary.alloc(size_t(n_nodes) * sizeof(rayhip_light_refit::Summary))) {
-        return 1;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream)); // the three vectors go out of scope
-    lr.ready = true;
-    return 0;
-}
-
+// lights, their index list, the light tree (+ its per-node importance table) and the world-space corners of the triangle
+// lights: everything an instance / light change replaces besides the top-level tree
 static int upload_lights(rayhip_ctx *c, const rayhip_scene_desc *d) {
     c->light_refit.ready = false;
     c->light_refit.lights_count = d->lights_count, c->light_refit.li_count = d->li_indices_count, c->light_refit.nodes_count = d->light_cwnodes_count;
@@ -173,8 +141,6 @@ static int upload_lights(rayhip_ctx *c, const rayhip_scene_desc *d) {
     return 0;
 }
 
-
-// the kernels' view of what is on the device (SceneView), after a full upload or an instance update
 // distinct instances the top level of a (validated) scene holds: a leaf word of the top level stands for one instance (the reference's
 // one-leaf tree is a root whose two links are the same leaf word, the second one behind a point box at the origin: Core.cpp:1191-1213)
 static uint32_t count_top_level_instances(const rayhip_bvh2_node *nodes, const uint32_t nodes_count, const uint32_t root) {
@@ -216,6 +182,7 @@ static void refresh_top_level_view(rayhip_ctx *c, const uint32_t tlas_root, cons
     }
 }
 
+// the kernels' view of what is on the device (SceneView), after a full upload or an instance update
 static void refresh_scene_view(rayhip_ctx *c, const rayhip_scene_desc *d, const uint32_t tlas_root, const rayhip_lbvh::Box &root_box,
                                const uint32_t live_instances) {
     SceneView &v = c->sc;
@@ -252,99 +219,6 @@ static void refresh_scene_view(rayhip_ctx *c, const rayhip_scene_desc *d, const 
     refresh_top_level_view(c, tlas_root, root_box, live_instances);
 }
 
-
-// ---- what a later rayhip_scene_update_vertices needs of an upload (refit.h) -----------------------------------------------------
-// the bottom-level nodes sorted by height and the first entry of every triangle, on the device; the root list of the collapse; the
-// live instances and the instance array on the host.  `nodes` / `instances` / `tri_indices`: the arrays as uploaded.
-static int prepare_refit(rayhip_ctx *c, const rayhip_bvh2_node *nodes, const uint32_t nodes_count, const rayhip_mesh_instance *instances,
-                         const uint32_t instances_count, const uint32_t tlas_root, const uint32_t *tri_indices, const uint32_t entries,
-                         const uint32_t *vtx_indices, const uint32_t n_tris, const uint32_t n_vertices, const bool rebased_for_bvh8) {
-    rayhip_ctx::Refit &r = c->refit;
-    r.level_offset.clear(), r.roots.clear(), r.ordinal_of_root.clear(), r.live.clear();
-    r.levels_rc = 2, r.entries = entries, r.degenerate = 0;
-    // the vertices some triangle of the table uses: the vertex array is a sparse pool, a free slot may hold anything
-    r.vertex_used.assign(n_vertices, 0);
-    for (uint32_t e = 0; e < entries; ++e) {
-        for (uint32_t k = 0; tri_indices[e] < n_tris && k < 3; ++k) {
-            const uint32_t v = vtx_indices[size_t(tri_indices[e]) * 3 + k];
-            if (v < n_vertices) {
-                r.vertex_used[v] = 1;
-            }
-        }
-    }
-    r.instances.assign(instances, instances + instances_count);
-    std::vector<std::pair<uint32_t, uint32_t>> top;
-    if (tlas_root != 0xffffffffu && rayhip_rebuild::collect_leaf_ranges(nodes, nodes_count, tlas_root, top)) {
-        for (const auto &leaf : top) {
-            r.live.push_back(leaf.first);
-        }
-        std::sort(r.live.begin(), r.live.end());
-        r.live.erase(std::unique(r.live.begin(), r.live.end()), r.live.end());
-    }
-    if (rebased_for_bvh8) {
-        return 0; // (the 8-wide builder is host-only: such a context refuses the vertex update)
-    }
-    std::vector<uint32_t> root_of_instance;
-    if (!rayhip_bvh4::collect_roots(nodes, nodes_count, instances, instances_count, tlas_root, r.roots, root_of_instance)) {
-        r.roots.clear();
-    }
-    for (size_t k = 0; k < r.roots.size(); ++k) {
-        r.ordinal_of_root[r.roots[k]] = uint32_t(k);
-    }
-    std::vector<uint32_t> level_nodes;
-    r.levels_rc = rayhip_refit::plan_levels(nodes, nodes_count, r.roots, level_nodes, r.level_offset);
-    if (r.levels_rc != 0) {
-        return 0; // (a tree above 128 levels: the update says so when it is asked for)
-    }
-    const std::vector<uint32_t> first = rayhip_refit::first_entries(tri_indices, entries, n_tris);
-    if (upload(c, r.level_nodes, level_nodes.data(), level_nodes.size() * sizeof(uint32_t)) ||
-        upload(c, r.first_entry, first.data(), first.size() * sizeof(uint32_t)) ||
-        r.scratch.alloc(256 + r.roots.size() * (sizeof(uint32_t) + sizeof(rayhip_bvh2_node)) + 64)) {
-        return 1;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream)); // the two vectors go out of scope
-    return 0;
-}
-
-// the vertices some triangle light's triangle uses, as they are on the device: the light arrays are not rebuilt by a vertex update,
-// so it refuses to move one of these
-static void keep_light_vertices(rayhip_ctx *c, const rayhip_scene_desc *d) {
-    std::vector<std::pair<uint32_t, rayhip_vertex>> &kept = c->refit.light_vertices;
-    kept.clear();
-    for (uint32_t k = 0; k < d->li_indices_count; ++k) {
-        const uint32_t i = d->li_indices[k];
-        if (i >= d->lights_count || light_type(d->lights[i]) != LIGHT_TYPE_TRI) {
-            continue;
-        }
-        const size_t tri = float_as_uint(d->lights[i].params[0]);
-        for (size_t j = tri * 3; j < tri * 3 + 3 && j < d->vtx_indices_count; ++j) {
-            if (d->vtx_indices[j] < d->vertices_count) {
-                kept.emplace_back(d->vtx_indices[j], d->vertices[d->vtx_indices[j]]);
-            }
-        }
-    }
-    std::sort(kept.begin(), kept.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
-    kept.erase(std::unique(kept.begin(), kept.end(), [](const auto &x, const auto &y) { return x.first == y.first; }), kept.end());
-}
-
-// ... and on the device, with the per-vertex `used` flags, for the updates whose vertices never pass through the host
-// (k_skin_vertices, k_check_vertices: skin.hip.h).  `with_used`: the flags too (they change with an upload only).
-static int upload_vertex_checks(rayhip_ctx *c, const bool with_used) {
-    rayhip_ctx::Refit &r = c->refit;
-    std::vector<uint32_t> index(r.light_vertices.size());
-    std::vector<rayhip_vertex> kept(r.light_vertices.size());
-    for (size_t k = 0; k < r.light_vertices.size(); ++k) {
-        index[k] = r.light_vertices[k].first, kept[k] = r.light_vertices[k].second;
-    }
-    if (upload(c, r.d_light_index, index.data(), index.size() * sizeof(uint32_t)) ||
-        upload(c, r.d_light_vertices, kept.data(), kept.size() * sizeof(rayhip_vertex)) ||
-        (with_used && upload(c, r.d_vertex_used, r.vertex_used.data(), r.vertex_used.size()))) {
-        return 1;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream)); // the two vectors go out of scope
-    return 0;
-}
-
 // The top level of `up` built ON THE DEVICE by the linear builder and written behind the uploaded nodes: two halves, used in turn --
 // the tree the scene view still points at is never overwritten, so a failure further down (rc 1) leaves a context that renders the
 // previous top level.  0 = ok, 1 = error, 2 = no room (a full upload reserves anew).
@@ -377,110 +251,173 @@ static int rebuild_top_level(rayhip_ctx *c, const rayhip_update::Plan &up, uint3
     return 0;
 }
 
-#define UPLOAD_TRACE(msg)                                                                                              \
-    if (getenv("RAYHIP_TRACE_UPLOAD")) {                                                                               \
-        fprintf(stderr, "rayhip_scene_upload: %8.1f ms  %s\n",                                                         \
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - upload_t0).count(), msg);  \
+// the stamps of an upload or instance update (RAYHIP_TRACE_UPLOAD): host time since the start of the call
+struct UploadTrace {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void operator()(const char *msg) const {
+        if (getenv("RAYHIP_TRACE_UPLOAD")) {
+            fprintf(stderr, "rayhip_scene_upload: %8.1f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), msg);
+        }
     }
+};
 
-int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
-    if (use_device(c)) {
-        return 1;
-    }
-    if (d_in->struct_size != sizeof(rayhip_scene_desc)) { // (before anything else of the struct is looked at)
+// ---- the checks rayhip_scene_upload and rayhip_scene_update_instances share --------------------------------------------------------------
+static int check_struct_size(const rayhip_scene_desc *d) { // (before anything else of the struct is looked at)
+    if (d->struct_size != sizeof(rayhip_scene_desc)) {
         return fail("rayhip_scene_desc::struct_size is %u, this library's struct has %zu bytes (ABI version %d): the caller was built against another rayhip.h",
-                    d_in->struct_size, sizeof(rayhip_scene_desc), RAYHIP_ABI_VERSION);
+                    d->struct_size, sizeof(rayhip_scene_desc), RAYHIP_ABI_VERSION);
     }
-    const auto upload_t0 = std::chrono::steady_clock::now();
-    (void)upload_t0;
-    UPLOAD_TRACE("begin")
-    c->discard_skins(); // (a skin names a range of the vertex array this call replaces)
-    const rayhip_layout::AlignedDesc aligned(*d_in); // see bvh_layout.h
-    const rayhip_scene_desc *d = &aligned.d;
-    if (d->env.qtree_levels < 0 || d->env.qtree_levels > 16) {
-        return fail("bad env-map quadtree depth %d", d->env.qtree_levels);
+    return 0;
+}
+
+// (the depth was checked: 0 .. 16)
+static int check_env_qtree_size(const rayhip_scene_desc *d) {
+    size_t quads = 0;
+    for (int lod = 0; lod < d->env.qtree_levels; ++lod) {
+        quads += size_t(1) << (2 * (d->env.qtree_levels - 1 - lod));
     }
-    // (the physical sky, environment_t::sky_map_spread_angle > 0: narrow rays are evaluated analytically, rt_sky.h; what that needs
-    // arrives as rayhip_scene_desc::sky* and is checked by the validation below)
-    {
-        size_t quads = 0;
-        for (int lod = 0; lod < d->env.qtree_levels; ++lod) {
-            quads += size_t(1) << (2 * (d->env.qtree_levels - 1 - lod));
-        }
-        if (size_t(d->env_qtree_count) != quads * 4) {
-            return fail("env_qtree holds %u floats, %d levels need %zu", d->env_qtree_count, d->env.qtree_levels, quads * 4);
-        }
+    if (size_t(d->env_qtree_count) != quads * 4) {
+        return fail("env_qtree holds %u floats, %d levels need %zu", d->env_qtree_count, d->env.qtree_levels, quads * 4);
     }
-    bool all_sides_solid = false; // (over the triangles the trees reach: the pools are sparse, an unused slot is all zeros)
-    { // every index a kernel would follow without a bound of its own (scene_validate.h)
-        std::string why;
-        if (!rayhip_validate::validate(*d, why, &all_sides_solid)) {
-            return fail("%s", why.c_str());
-        }
-    }
-    UPLOAD_TRACE("validated")
-    // Leaf refinement (scene_rebuild.h): the scene's trees are kept, every leaf with more than `leaf_max` triangles is replaced
-    // by a subtree of the linear builder.  RAYHIP_REFINE_LEAVES=<leaf_max> (0 = leave the trees as they are; default 2).
-    // RAYHIP_REBUILD_BVH=<leaf_max>: both levels rebuilt from the triangles and instance transforms instead (lbvh.h).
-    rayhip_rebuild::Rebuilt rebuilt;
-    rayhip_scene_desc d_rebuilt = *d;
-    {
-        int refine = 2, rebuild = 0;
-        if (const char *e = getenv("RAYHIP_REFINE_LEAVES")) {
-            refine = std::max(0, std::min(8, atoi(e)));
-        }
-        if (const char *e = getenv("RAYHIP_REBUILD_BVH")) {
-            rebuild = std::max(0, std::min(8, atoi(e)));
-        }
-        if (rebuild > 0 || refine > 0) {
-            // the builder itself runs on the device (lbvh.hip.h); RAYHIP_BVH_BUILD_ON_HOST=1 runs the same element functions
-            // as host loops instead (A/B and debugging: the two produce identical arrays)
-            const bool on_host = getenv("RAYHIP_BVH_BUILD_ON_HOST") != nullptr && atoi(getenv("RAYHIP_BVH_BUILD_ON_HOST")) != 0;
-            auto build = [&](const rayhip_lbvh::Input &in, rayhip_lbvh::Output &out, std::string &why) {
-                if (on_host) {
-                    out = rayhip_lbvh::build_host(in);
-                    return true;
-                }
-                return rayhip_lbvh::build_device(c->stream, in, out, why);
-            };
-            rebuilt = rebuild > 0 ? rayhip_rebuild::rebuild_with(*d, uint32_t(rebuild), build) : rayhip_rebuild::refine_with(*d, uint32_t(refine), build);
-            UPLOAD_TRACE(rebuild > 0 ? "both levels rebuilt" : "leaves refined")
-            if (!rebuilt.ok) {
-                return fail("acceleration-structure %s failed: %s", rebuild > 0 ? "rebuild" : "refinement", rebuilt.why.c_str());
-            }
-            d_rebuilt.nodes = rebuilt.nodes.data(), d_rebuilt.nodes_count = uint32_t(rebuilt.nodes.size());
-            d_rebuilt.tris = rebuilt.tris.data(), d_rebuilt.tris_count = uint32_t(rebuilt.tris.size());
-            d_rebuilt.tri_indices = rebuilt.tri_indices.data(), d_rebuilt.tri_indices_count = uint32_t(rebuilt.tri_indices.size());
-            d_rebuilt.mesh_instances = rebuilt.mesh_instances.data();
-            d_rebuilt.tlas_root = rebuilt.tlas_root;
-            d = &d_rebuilt;
-            std::string why;
-            if (!rayhip_validate::validate(*d, why)) {
-                return fail("rebuilt scene: %s", why.c_str());
-            }
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- the phases of rayhip_scene_upload, in the order they run ---------------------------------------------------------------------------
+// A phase that starts a copy from one of its own host arrays waits for the stream before it returns.
 #define UP(field)                                                                                                      \
     if (upload(c, c->field, d->field, size_t(d->field##_count) * sizeof(*d->field))) {                                 \
         return 1;                                                                                                      \
     }
-    // HBM layout pass (bvh_layout.h): depth-first node order with sibling pairs in one 128-byte line, triangles in
-    // leaf-visit order.  Off by default since round 3 (RAYHIP_LAYOUT=1 switches it on): the kernels walk the 4-wide collapse,
-    // whose node order is the collapse's own, and the triangle records come out of the leaf refinement grouped leaf by leaf
-    // in the order of a depth-first walk already -- measured, Bistro-class scene: K2 2.11 ms per iteration with the pass,
-    // 2.13 without, Sponza-class 1.70 / 1.70 (profiles/r03/experiments/variants_layout_*.txt) -- for 181 ms of host time
-    // per upload.  Without leaf refinement (RAYHIP_REFINE_LEAVES=0) the pass still runs: the reference builder's order is poor.
-    rayhip_layout::Result lay;
-    {
-        const char *e = getenv("RAYHIP_LAYOUT"), *off = getenv("RAYHIP_NO_LAYOUT");
-        const bool want_layout = e ? e[0] == '1' : !rebuilt.ok;
-        if (want_layout && !(off && off[0] == '1')) {
-            lay = rayhip_layout::optimize(*d);
+
+// Leaf refinement (scene_rebuild.h): the scene's trees are kept, every leaf with more than `leaf_max` triangles is replaced
+// by a subtree of the linear builder.  RAYHIP_REFINE_LEAVES=<leaf_max> (0 = leave the trees as they are; default 2).
+// RAYHIP_REBUILD_BVH=<leaf_max>: both levels rebuilt from the triangles and instance transforms instead (lbvh.h).
+// `rebuilt`: the new arrays (ok: there are some), `out`: `d` with its trees replaced by them.
+static int refine_trees(rayhip_ctx *c, const rayhip_scene_desc *d, const bool build_on_host, const UploadTrace &trace, rayhip_rebuild::Rebuilt &rebuilt,
+                        rayhip_scene_desc &out) {
+    int refine = 2, rebuild = 0;
+    if (const char *e = getenv("RAYHIP_REFINE_LEAVES")) {
+        refine = std::max(0, std::min(8, atoi(e)));
+    }
+    if (const char *e = getenv("RAYHIP_REBUILD_BVH")) {
+        rebuild = std::max(0, std::min(8, atoi(e)));
+    }
+    if (rebuild > 0 || refine > 0) {
+        // the builder itself runs on the device (lbvh.hip.h); RAYHIP_BVH_BUILD_ON_HOST=1 runs the same element functions
+        // as host loops instead (A/B and debugging: the two produce identical arrays)
+        auto build = [&](const rayhip_lbvh::Input &in, rayhip_lbvh::Output &built, std::string &why) {
+            if (build_on_host) {
+                built = rayhip_lbvh::build_host(in);
+                return true;
+            }
+            return rayhip_lbvh::build_device(c->stream, in, built, why);
+        };
+        rebuilt = rebuild > 0 ? rayhip_rebuild::rebuild_with(*d, uint32_t(rebuild), build) : rayhip_rebuild::refine_with(*d, uint32_t(refine), build);
+        trace(rebuild > 0 ? "both levels rebuilt" : "leaves refined");
+        if (!rebuilt.ok) {
+            return fail("acceleration-structure %s failed: %s", rebuild > 0 ? "rebuild" : "refinement", rebuilt.why.c_str());
+        }
+        out.nodes = rebuilt.nodes.data(), out.nodes_count = uint32_t(rebuilt.nodes.size());
+        out.tris = rebuilt.tris.data(), out.tris_count = uint32_t(rebuilt.tris.size());
+        out.tri_indices = rebuilt.tri_indices.data(), out.tri_indices_count = uint32_t(rebuilt.tri_indices.size());
+        out.mesh_instances = rebuilt.mesh_instances.data();
+        out.tlas_root = rebuilt.tlas_root;
+        std::string why;
+        if (!rayhip_validate::validate(out, why)) {
+            return fail("rebuilt scene: %s", why.c_str());
         }
     }
-    UPLOAD_TRACE(lay.applied ? "layout applied" : lay.why_not)
-    uint32_t tlas_root = d->tlas_root;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// HBM layout pass (bvh_layout.h): depth-first node order with sibling pairs in one 128-byte line, triangles in
+// leaf-visit order.  Off by default since round 3 (RAYHIP_LAYOUT=1 switches it on): the kernels walk the 4-wide collapse,
+// whose node order is the collapse's own, and the triangle records come out of the leaf refinement grouped leaf by leaf
+// in the order of a depth-first walk already -- measured, Bistro-class scene: K2 2.11 ms per iteration with the pass,
+// 2.13 without, Sponza-class 1.70 / 1.70 (profiles/r03/experiments/variants_layout_*.txt) -- for 181 ms of host time
+// per upload.  Without leaf refinement (RAYHIP_REFINE_LEAVES=0) the pass still runs: the reference builder's order is poor.
+static rayhip_layout::Result layout_pass(const rayhip_scene_desc *d, const bool refined) {
+    const char *e = getenv("RAYHIP_LAYOUT"), *off = getenv("RAYHIP_NO_LAYOUT");
+    const bool want_layout = e ? e[0] == '1' : !refined;
+    if (want_layout && !(off && off[0] == '1')) {
+        return rayhip_layout::optimize(*d);
+    }
+    return rayhip_layout::Result();
+}
+
+// the walks' triangle table: the reference's 48-byte array as it is; RAYHIP_TRI_PITCH=64 re-pitches it so that every record lies in
+// its own 64-byte sector (half of the 48-byte records straddle two) -- measured neutral (K2 2.14 against 2.12 ms,
+// profiles/r03/experiments/variants_tripitch.txt: the kernel is bound by instruction issue, not by sectors), so it stays an option
+static int pitch_tris(rayhip_ctx *c, const size_t n_tris) {
+    c->tri_pitch = 3;
+    if (n_tris && getenv("RAYHIP_TRI_PITCH") && atoi(getenv("RAYHIP_TRI_PITCH")) == 64) {
+        DevBuf padded;
+        if (padded.alloc(n_tris * 64)) {
+            return 1;
+        }
+        k_pad_tris<<<unsigned((n_tris * 4 + 255) / 256), 256, 0, c->stream>>>(c->tris.as<float4>(), padded.as<float4>(), n_tris);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->tris.swap(padded);
+        padded.release();
+        c->tri_pitch = 4;
+    }
+    return 0;
+}
+
+// The 4-wide collapse: on the device over the nodes just uploaded (bvh4_build.hip.h); RAYHIP_BVH_BUILD_ON_HOST=1: the host driver
+// over the same element functions (A/B: the same tree in another node order).  `wide` = 4 and `blas_root4` filled, or both left /
+// emptied: the kernels walk the BVH2 for this scene.
+static int collapse_bvh4(rayhip_ctx *c, const rayhip_bvh2_node *n2, const uint32_t n2_count, const rayhip_mesh_instance *mis, const uint32_t mis_count,
+                         const uint32_t tlas_root, const bool build_on_host, int &wide, std::vector<uint32_t> &blas_root4, size_t &wide_bytes) {
+    if (build_on_host) {
+        rayhip_bvh4::Result b4 = rayhip_bvh4::build(n2, n2_count, mis, mis_count, tlas_root);
+        if (b4.ok && !b4.nodes.empty()) {
+            if (upload(c, c->nodes4, b4.nodes.data(), b4.nodes.size() * sizeof(Bvh4Node)) ||
+                upload(c, c->blas_root4, b4.blas_root4.data(), b4.blas_root4.size() * sizeof(uint32_t))) {
+                return 1;
+            }
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            wide = 4, blas_root4 = b4.blas_root4, wide_bytes = b4.nodes.size() * sizeof(Bvh4Node);
+        }
+        return 0;
+    }
+    std::vector<uint32_t> roots;
+    uint32_t n_wide = 0;
+    std::string why;
+    if (!rayhip_bvh4::collect_roots(n2, n2_count, mis, mis_count, tlas_root, roots, blas_root4) || roots.empty()) {
+        blas_root4.clear();
+        return 0;
+    }
+    if (c->nodes4.alloc(size_t(n2_count) * sizeof(Bvh4Node))) {
+        return 1;
+    }
+    bool unquantisable = false;
+    if (!rayhip_bvh4::build_device(c->stream, c->nodes.as<rayhip_bvh2_node>(), n2_count, roots, c->nodes4.as<Bvh4Node>(), n_wide, why, &unquantisable)) {
+        if (!unquantisable) {
+            return fail("4-wide collapse failed: %s", why.c_str()); // (a HIP error)
+        }
+        // a box the grid cannot hold: the kernels walk the BVH2 for this scene, as the host builder documents (bvh4_build.h)
+        blas_root4.clear();
+        return 0;
+    }
+    if (upload(c, c->blas_root4, blas_root4.data(), blas_root4.size() * sizeof(uint32_t))) { // (the caller's vector: it waits)
+        return 1;
+    }
+    wide = 4, wide_bytes = size_t(n_wide) * sizeof(Bvh4Node);
+    return 0;
+}
+
+// The bottom level: nodes, triangle records and instances in the order `lay` decided (or the scene's own), and the wide quantised
+// BLAS trees over that node order.  RAYHIP_BVH_WIDTH: 4 (default; rt_bvh4.h), 8 (rt_bvh8.h -- it also decides the order of the
+// triangle records and re-bases the BVH2's leaf words onto it; a scene it cannot take gets the 4-wide form), 2 keeps the kernels on
+// the reference's BVH2 (RAYHIP_NO_BVH4=1 says the same; A/B measurements).  Leaves behind what the later updates need
+// (collect_mesh_refs, prepare_refit).  `wide`: the form built (0: none), `tlas_root`: the top level's root on the device.
+static int upload_bottom_level(rayhip_ctx *c, const rayhip_scene_desc *d, rayhip_layout::Result &lay, const bool build_on_host, const UploadTrace &trace,
+                               int &wide, uint32_t &tlas_root) {
+    wide = 0;
+    tlas_root = lay.applied ? lay.tlas_root : d->tlas_root;
     { // room behind the nodes for top-level trees rebuilt on the device later (rayhip_scene_update_instances)
         const size_t n_now = lay.applied ? lay.nodes.size() : size_t(d->nodes_count);
         c->nodes_used = uint32_t(n_now);
@@ -490,135 +427,81 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
             return 1;
         }
     }
+    // Default 4: measured on the MI355X (profiles/r03/experiments/variants_bvh8.txt) the 8-wide walk performs 29 % fewer node
+    // visits and 17 % more triangle tests per ray and takes the same time -- 2.17 vs 2.11 ms per iteration on the Bistro-class
+    // scene, within 1 % on the other workloads: the kernel is bound by random cache-line fetches per second, and an 80-byte
+    // node costs two 64-byte sectors.  The narrower form needs no dynamic-programming collapse at upload (0.5 s) either.
+    int want = 4;
+    if (const char *e = getenv("RAYHIP_BVH_WIDTH")) {
+        want = atoi(e);
+    }
+    if (const char *e = getenv("RAYHIP_NO_BVH4")) {
+        want = e[0] == '1' ? 2 : want;
+    }
+    std::vector<rayhip_bvh2_node> nodes2_own; // a copy the 8-wide build may re-base (the caller's arrays are const)
+    rayhip_bvh2_node *n2 = nullptr;
     if (lay.applied) {
-        tlas_root = lay.tlas_root;
+        n2 = lay.nodes.data();
+    } else {
+        nodes2_own.assign(d->nodes, d->nodes + d->nodes_count);
+        n2 = nodes2_own.data();
     }
-    // Wide quantised BLAS trees over the node order just decided.  RAYHIP_BVH_WIDTH: 8 (default; rt_bvh8.h -- it also decides the
-    // order of the triangle records and re-bases the BVH2's leaf words onto it), 4 (rt_bvh4.h: round 2's form), 2 keeps the
-    // kernels on the reference's BVH2 (RAYHIP_NO_BVH4=1 says the same; A/B measurements)
-    int wide = 0;
+    const uint32_t n2_count = lay.applied ? uint32_t(lay.nodes.size()) : d->nodes_count;
+    const rayhip_mesh_instance *mis = lay.applied ? lay.mesh_instances.data() : d->mesh_instances;
+    const rayhip_tri_accel *tris_in = lay.applied ? lay.tris.data() : d->tris;
+    const uint32_t *tri_indices_in = lay.applied ? lay.tri_indices.data() : d->tri_indices;
+    size_t n_tris = lay.applied ? lay.tris.size() : size_t(d->tris_count);
+    rayhip_bvh8::Result b8;
+    if (want == 8) {
+        b8 = rayhip_bvh8::build(n2, n2_count, mis, d->mesh_instances_count, tlas_root, tris_in, tri_indices_in, uint32_t(n_tris));
+        trace(b8.ok ? "bvh8 built" : b8.why_not);
+    }
+    const bool have8 = b8.ok && !b8.nodes.empty();
+    if (have8) {
+        tris_in = b8.tris.data(), tri_indices_in = b8.tri_indices.data(), n_tris = b8.tris.size();
+    }
+    if (upload(c, c->nodes, n2, size_t(n2_count) * sizeof(rayhip_bvh2_node)) ||
+        upload(c, c->tris, tris_in, n_tris * sizeof(rayhip_tri_accel)) ||
+        upload(c, c->tri_indices, tri_indices_in, n_tris * sizeof(uint32_t)) ||
+        upload(c, c->mesh_instances, mis, size_t(d->mesh_instances_count) * sizeof(rayhip_mesh_instance))) {
+        return 1;
+    }
+    c->instances_count = d->mesh_instances_count;
+    if (pitch_tris(c, n_tris)) {
+        return 1;
+    }
     std::vector<uint32_t> blas_root4;
-    {
-        // Default 4: measured on the MI355X (profiles/r03/experiments/variants_bvh8.txt) the 8-wide walk performs 29 % fewer node
-        // visits and 17 % more triangle tests per ray and takes the same time -- 2.17 vs 2.11 ms per iteration on the Bistro-class
-        // scene, within 1 % on the other workloads: the kernel is bound by random cache-line fetches per second, and an 80-byte
-        // node costs two 64-byte sectors.  The narrower form needs no dynamic-programming collapse at upload (0.5 s) either.
-        int want = 4;
-        if (const char *e = getenv("RAYHIP_BVH_WIDTH")) {
-            want = atoi(e);
-        }
-        if (const char *e = getenv("RAYHIP_NO_BVH4")) {
-            want = e[0] == '1' ? 2 : want;
-        }
-        std::vector<rayhip_bvh2_node> nodes2_own; // a copy the 8-wide build may re-base (the caller's arrays are const)
-        rayhip_bvh2_node *n2 = nullptr;
-        if (lay.applied) {
-            n2 = lay.nodes.data();
-        } else {
-            nodes2_own.assign(d->nodes, d->nodes + d->nodes_count);
-            n2 = nodes2_own.data();
-        }
-        const uint32_t n2_count = lay.applied ? uint32_t(lay.nodes.size()) : d->nodes_count;
-        const rayhip_mesh_instance *mis = lay.applied ? lay.mesh_instances.data() : d->mesh_instances;
-        const rayhip_tri_accel *tris_in = lay.applied ? lay.tris.data() : d->tris;
-        const uint32_t *tri_indices_in = lay.applied ? lay.tri_indices.data() : d->tri_indices;
-        size_t n_tris = lay.applied ? lay.tris.size() : size_t(d->tris_count);
-        rayhip_bvh8::Result b8;
-        if (want == 8) {
-            b8 = rayhip_bvh8::build(n2, n2_count, mis, d->mesh_instances_count, tlas_root, tris_in, tri_indices_in, uint32_t(n_tris));
-            UPLOAD_TRACE(b8.ok ? "bvh8 built" : b8.why_not)
-        }
-        if (b8.ok && !b8.nodes.empty()) {
-            tris_in = b8.tris.data(), tri_indices_in = b8.tri_indices.data(), n_tris = b8.tris.size();
-        }
-        if (upload(c, c->nodes, n2, size_t(n2_count) * sizeof(rayhip_bvh2_node)) ||
-            upload(c, c->tris, tris_in, n_tris * sizeof(rayhip_tri_accel)) ||
-            upload(c, c->tri_indices, tri_indices_in, n_tris * sizeof(uint32_t)) ||
-            upload(c, c->mesh_instances, mis, size_t(d->mesh_instances_count) * sizeof(rayhip_mesh_instance))) {
+    size_t wide_bytes = 0;
+    if (have8) {
+        if (upload(c, c->nodes8, b8.nodes.data(), b8.nodes.size() * sizeof(Bvh8Node)) ||
+            upload(c, c->blas_root4, b8.blas_root8.data(), b8.blas_root8.size() * sizeof(uint32_t))) {
             return 1;
         }
-        c->instances_count = d->mesh_instances_count;
-        // the walks' triangle table: the reference's 48-byte array as it is; RAYHIP_TRI_PITCH=64 re-pitches it so that every record lies in
-        // its own 64-byte sector (half of the 48-byte records straddle two) -- measured neutral (K2 2.14 against 2.12 ms,
-        // profiles/r03/experiments/variants_tripitch.txt: the kernel is bound by instruction issue, not by sectors), so it stays an option
-        c->tri_pitch = 3;
-        if (n_tris && getenv("RAYHIP_TRI_PITCH") && atoi(getenv("RAYHIP_TRI_PITCH")) == 64) {
-            DevBuf padded;
-            if (padded.alloc(n_tris * 64)) {
-                return 1;
-            }
-            k_pad_tris<<<unsigned((n_tris * 4 + 255) / 256), 256, 0, c->stream>>>(c->tris.as<float4>(), padded.as<float4>(), n_tris);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            c->tris.swap(padded);
-            padded.release();
-            c->tri_pitch = 4;
-        }
-        size_t wide_bytes = 0;
-        if (b8.ok && !b8.nodes.empty()) {
-            if (upload(c, c->nodes8, b8.nodes.data(), b8.nodes.size() * sizeof(Bvh8Node)) ||
-                upload(c, c->blas_root4, b8.blas_root8.data(), b8.blas_root8.size() * sizeof(uint32_t))) {
-                return 1;
-            }
-            wide = 8, blas_root4 = b8.blas_root8, wide_bytes = b8.nodes.size() * sizeof(Bvh8Node);
-        } else if (want == 4 || want == 8) {
-            // the collapse runs on the device over the nodes just uploaded (bvh4_build.hip.h); RAYHIP_BVH_BUILD_ON_HOST=1: the host
-            // driver over the same element functions (A/B: the same tree in another node order)
-            const bool on_host = getenv("RAYHIP_BVH_BUILD_ON_HOST") != nullptr && atoi(getenv("RAYHIP_BVH_BUILD_ON_HOST")) != 0;
-            if (on_host) {
-                rayhip_bvh4::Result b4 = rayhip_bvh4::build(n2, n2_count, mis, d->mesh_instances_count, tlas_root);
-                if (b4.ok && !b4.nodes.empty()) {
-                    if (upload(c, c->nodes4, b4.nodes.data(), b4.nodes.size() * sizeof(Bvh4Node)) ||
-                        upload(c, c->blas_root4, b4.blas_root4.data(), b4.blas_root4.size() * sizeof(uint32_t))) {
-                        return 1;
-                    }
-                    HIP_TRY(hipStreamSynchronize(c->stream));
-                    wide = 4, blas_root4 = b4.blas_root4, wide_bytes = b4.nodes.size() * sizeof(Bvh4Node);
-                }
-            } else {
-                std::vector<uint32_t> roots;
-                uint32_t n_wide = 0;
-                std::string why;
-                if (rayhip_bvh4::collect_roots(n2, n2_count, mis, d->mesh_instances_count, tlas_root, roots, blas_root4) && !roots.empty()) {
-                    if (c->nodes4.alloc(size_t(n2_count) * sizeof(Bvh4Node))) {
-                        return 1;
-                    }
-                    bool unquantisable = false;
-                    if (!rayhip_bvh4::build_device(c->stream, c->nodes.as<rayhip_bvh2_node>(), n2_count, roots, c->nodes4.as<Bvh4Node>(), n_wide, why, &unquantisable)) {
-                        if (!unquantisable) {
-                            return fail("4-wide collapse failed: %s", why.c_str()); // (a HIP error)
-                        }
-                        // a box the grid cannot hold: the kernels walk the BVH2 for this scene, as the host builder documents (bvh4_build.h)
-                        blas_root4.clear();
-                    } else {
-                        if (upload(c, c->blas_root4, blas_root4.data(), blas_root4.size() * sizeof(uint32_t))) {
-                            return 1;
-                        }
-                        wide = 4, wide_bytes = size_t(n_wide) * sizeof(Bvh4Node);
-                    }
-                } else {
-                    blas_root4.clear();
-                }
-            }
-            UPLOAD_TRACE(wide == 4 ? "bvh4 built" : "no wide BLAS")
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream)); // the builders' arrays go out of scope
-        // "small": the BLAS working set (nodes + triangle records) fits one XCD's 4 MB L2 with room to spare
-        c->small_scene = wide != 0 && getenv("RAYHIP_NO_SMALL") == nullptr && wide_bytes + n_tris * sizeof(rayhip_tri_accel) <= (size_t(2) << 20);
-        // the meshes in use, for rayhip_scene_update_instances: the roots of their trees as uploaded
-        rayhip_update::collect_mesh_refs(n2, n2_count, mis, d->mesh_instances_count, tlas_root, wide ? blas_root4.data() : nullptr, c->mesh_refs);
-        // ... and for rayhip_scene_update_vertices: the bottom-level nodes by height, the live instances (refit.h)
-        if (prepare_refit(c, n2, n2_count, mis, d->mesh_instances_count, tlas_root, tri_indices_in, uint32_t(n_tris), d->vtx_indices,
-                          d->vtx_indices_count / 3, d->vertices_count, b8.ok && !b8.nodes.empty())) {
+        wide = 8, blas_root4 = b8.blas_root8, wide_bytes = b8.nodes.size() * sizeof(Bvh8Node);
+    } else if (want == 4 || want == 8) {
+        if (collapse_bvh4(c, n2, n2_count, mis, d->mesh_instances_count, tlas_root, build_on_host, wide, blas_root4, wide_bytes)) {
             return 1;
         }
+        trace(wide == 4 ? "bvh4 built" : "no wide BLAS");
     }
-    UPLOAD_TRACE("bvh uploaded")
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the builders' arrays go out of scope
+    // "small": the BLAS working set (nodes + triangle records) fits one XCD's 4 MB L2 with room to spare
+    c->small_scene = wide != 0 && getenv("RAYHIP_NO_SMALL") == nullptr && wide_bytes + n_tris * sizeof(rayhip_tri_accel) <= (size_t(2) << 20);
+    // the meshes in use, for rayhip_scene_update_instances: the roots of their trees as uploaded
+    rayhip_update::collect_mesh_refs(n2, n2_count, mis, d->mesh_instances_count, tlas_root, wide ? blas_root4.data() : nullptr, c->mesh_refs);
+    // ... and for rayhip_scene_update_vertices: the bottom-level nodes by height, the live instances (refit.h)
+    return prepare_refit(c, n2, n2_count, mis, d->mesh_instances_count, tlas_root, tri_indices_in, uint32_t(n_tris), d->vtx_indices, d->vtx_indices_count / 3,
+                         d->vertices_count, have8);
+}
+
+// the arrays the shade stage reads: materials per triangle and their table, vertices and indices, and the vertices gathered per
+// triangle on the device from the arrays just uploaded (shade_point.h: fill_tri_verts)
+static int upload_shading_arrays(rayhip_ctx *c, const rayhip_scene_desc *d, const bool all_sides_solid, const UploadTrace &trace) {
     UP(tri_materials)
     // is there a triangle side that is not plainly solid?  (the closest-hit kernels skip the per-hit material fetch when not; round 4: judged
     // over the reachable triangles -- the headline scene's pool has unused slots, and the flag had never been set for it)
     c->all_solid = all_sides_solid ? 1u : 0u;
-    UPLOAD_TRACE(all_sides_solid ? "every reachable triangle side is solid" : "some triangle sides are not solid")
+    trace(all_sides_solid ? "every reachable triangle side is solid" : "some triangle sides are not solid");
     UP(materials)
     { // can any surface change a ray's stack of refractive indices?  (ShadeParams::plain_ior: if not, the passes leave the rays' ior plane alone)
         bool refracts = false;
@@ -627,57 +510,118 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
             refracts |= m.type == NODE_REFRACTIVE || (m.type == NODE_PRINCIPLED && m.transmission_unorm != 0);
         }
         c->plain_ior = !refracts && !getenv("RAYHIP_NO_PLAIN_IOR");
-        UPLOAD_TRACE(refracts ? "refractive surfaces: rays carry their ior stacks" : "no refractive surface: the ior plane of the rays is not used")
+        trace(refracts ? "refractive surfaces: rays carry their ior stacks" : "no refractive surface: the ior plane of the rays is not used");
     }
     UP(vertices)
     UP(vtx_indices)
-    { // vertices gathered per triangle (shade_point.h: fill_tri_verts), on the device from the arrays just uploaded
-        const uint32_t n_tris = d->vtx_indices_count / 3;
-        if (c->tri_verts.alloc(size_t(n_tris) * TRI_VERTS_STRIDE * sizeof(float4)) ||
-            c->tri_bitangents.alloc(size_t(n_tris) * TRI_BITANGENTS_STRIDE * sizeof(float4))) {
-            return 1;
-        }
-        if (n_tris) {
-            k_fill_tri_verts<<<(n_tris + 255) / 256, 256, 0, c->stream>>>(c->vertices.as<rayhip_vertex>(), d->vertices_count,
-                                                                          c->vtx_indices.as<uint32_t>(), n_tris,
-                                                                          c->tri_materials.as<rayhip_tri_mat_data>(), d->tri_materials_count,
-                                                                          c->tri_verts.as<float4>(), c->tri_bitangents.as<float4>());
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    UPLOAD_TRACE("tri_verts done")
-    if (upload_lights(c, d)) {
+    const uint32_t n_tris = d->vtx_indices_count / 3;
+    if (c->tri_verts.alloc(size_t(n_tris) * TRI_VERTS_STRIDE * sizeof(float4)) ||
+        c->tri_bitangents.alloc(size_t(n_tris) * TRI_BITANGENTS_STRIDE * sizeof(float4))) {
         return 1;
     }
-    keep_light_vertices(c, d);
-    if (upload_vertex_checks(c, true)) {
-        return 1;
+    if (n_tris) {
+        k_fill_tri_verts<<<(n_tris + 255) / 256, 256, 0, c->stream>>>(c->vertices.as<rayhip_vertex>(), d->vertices_count,
+                                                                      c->vtx_indices.as<uint32_t>(), n_tris,
+                                                                      c->tri_materials.as<rayhip_tri_mat_data>(), d->tri_materials_count,
+                                                                      c->tri_verts.as<float4>(), c->tri_bitangents.as<float4>());
+        HIP_TRY(hipGetLastError());
     }
-    UPLOAD_TRACE("lights done")
+    return 0;
+}
+
+// textures and the environment map's quadtree; the wait is for every copy from the caller's arrays since the last one
+static int upload_textures_and_env(rayhip_ctx *c, const rayhip_scene_desc *d) {
     UP(textures)
     UP(texels)
     UP(env_qtree)
-#undef UP
     HIP_TRY(hipStreamSynchronize(c->stream)); // host arrays may go away after this call
-    c->wide = wide;
     memcpy(c->tex_table, d->tex_table, sizeof(c->tex_table));
     c->textures_count = d->textures_count;
     c->tex_flags = d->texture_flags;
-    c->geometry = {d->vertices_count, d->vtx_indices_count, d->tri_materials_count, d->materials_count};
-    {
-        rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
-        if (d->tlas_root != 0xffffffffu && d->tlas_root < d->nodes_count) {
-            root_box = rayhip_rebuild::node_box(d->nodes[d->tlas_root]);
-        }
-        if (upload_sky(c, d)) {
-            return 1;
-        }
-        refresh_scene_view(c, d, tlas_root, root_box, count_top_level_instances(d->nodes, d->nodes_count, d->tlas_root));
+    return 0;
+}
+#undef UP
+
+int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
+    if (use_device(c) || check_struct_size(d_in)) {
+        return 1;
     }
+    const UploadTrace trace;
+    trace("begin");
+    c->discard_skins(); // (a skin names a range of the vertex array this call replaces)
+    const rayhip_layout::AlignedDesc aligned(*d_in); // see bvh_layout.h
+    const rayhip_scene_desc *d = &aligned.d;
+    if (d->env.qtree_levels < 0 || d->env.qtree_levels > 16) {
+        return fail("bad env-map quadtree depth %d", d->env.qtree_levels);
+    }
+    // (the physical sky, environment_t::sky_map_spread_angle > 0: narrow rays are evaluated analytically, rt_sky.h; what that needs
+    // arrives as rayhip_scene_desc::sky* and is checked by the validation below)
+    if (check_env_qtree_size(d)) {
+        return 1;
+    }
+    bool all_sides_solid = false; // (over the triangles the trees reach: the pools are sparse, an unused slot is all zeros)
+    { // every index a kernel would follow without a bound of its own (scene_validate.h)
+        std::string why;
+        if (!rayhip_validate::validate(*d, why, &all_sides_solid)) {
+            return fail("%s", why.c_str());
+        }
+    }
+    trace("validated");
+    const bool build_on_host = getenv("RAYHIP_BVH_BUILD_ON_HOST") != nullptr && atoi(getenv("RAYHIP_BVH_BUILD_ON_HOST")) != 0;
+    rayhip_rebuild::Rebuilt rebuilt; // (owns the arrays d_rebuilt names)
+    rayhip_scene_desc d_rebuilt = *d;
+    if (refine_trees(c, d, build_on_host, trace, rebuilt, d_rebuilt)) {
+        return 1;
+    }
+    if (rebuilt.ok) {
+        d = &d_rebuilt;
+    }
+    rayhip_layout::Result lay = layout_pass(d, rebuilt.ok);
+    trace(lay.applied ? "layout applied" : lay.why_not);
+    int wide = 0;
+    uint32_t tlas_root = 0xffffffffu;
+    if (upload_bottom_level(c, d, lay, build_on_host, trace, wide, tlas_root)) {
+        return 1;
+    }
+    trace("bvh uploaded");
+    if (upload_shading_arrays(c, d, all_sides_solid, trace)) {
+        return 1;
+    }
+    trace("tri_verts done");
+    if (upload_lights(c, d)) {
+        return 1;
+    }
+    keep_light_vertices(c, d); // (... and what a vertex update checks against them: rayhip_deform.hip.h)
+    if (upload_vertex_checks(c, true)) {
+        return 1;
+    }
+    trace("lights done");
+    if (upload_textures_and_env(c, d)) {
+        return 1;
+    }
+    c->wide = wide;
+    c->geometry = {d->vertices_count, d->vtx_indices_count, d->tri_materials_count, d->materials_count};
+    rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
+    if (d->tlas_root != 0xffffffffu && d->tlas_root < d->nodes_count) {
+        root_box = rayhip_rebuild::node_box(d->nodes[d->tlas_root]);
+    }
+    if (upload_sky(c, d)) {
+        return 1;
+    }
+    refresh_scene_view(c, d, tlas_root, root_box, count_top_level_instances(d->nodes, d->nodes_count, d->tlas_root));
     c->have_scene = true;
     c->census_valid = false; // (another scene: its queues fill differently; the next pass runs at full grids and takes a new census)
-    UPLOAD_TRACE("done")
+    trace("done");
     return 0;
+}
+
+int rayhip_scene_bvh_width(rayhip_ctx *c) { return !c || !c->have_scene ? 0 : c->wide ? c->wide : 2; }
+
+int rayhip_closest_hit_form(rayhip_ctx *c) {
+    if (!c || !c->have_scene || !c->wide || !c->refill_waves) {
+        return 0;
+    }
+    return (c->wide == 4 && c->refill_pool && c->pool_scene) ? 2 : 1;
 }
 
 // ---- instance / light / environment update without a new upload of the geometry -----------------------------------------
@@ -688,29 +632,15 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
 // device does not share after the layout pass) only tells which instance slots are alive and their world-space boxes.
 // Returns 0, 1 = error, 2 = the scene needs rayhip_scene_upload (an instance of a mesh that is not on the device, geometry
 // arrays of another size, no room for the tree).
-int rayhip_scene_bvh_width(rayhip_ctx *c) { return !c || !c->have_scene ? 0 : c->wide ? c->wide : 2; }
-
-int rayhip_closest_hit_form(rayhip_ctx *c) {
-    if (!c || !c->have_scene || !c->wide || !c->refill_waves) {
-        return 0;
-    }
-    return (c->wide == 4 && c->refill_pool && c->pool_scene) ? 2 : 1;
-}
-
 int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
-    if (use_device(c)) {
+    if (use_device(c) || check_struct_size(d)) {
         return 1;
-    }
-    if (d->struct_size != sizeof(rayhip_scene_desc)) {
-        return fail("rayhip_scene_desc::struct_size is %u, this library's struct has %zu bytes (ABI version %d): the caller was built against another rayhip.h",
-                    d->struct_size, sizeof(rayhip_scene_desc), RAYHIP_ABI_VERSION);
     }
     if (!c->have_scene) {
         (void)fail("rayhip_scene_update_instances before rayhip_scene_upload");
         return 2;
     }
-    const auto upload_t0 = std::chrono::steady_clock::now();
-    (void)upload_t0;
+    const UploadTrace trace;
     if (d->vertices_count != c->geometry.vertices || d->vtx_indices_count != c->geometry.vtx_indices ||
         d->tri_materials_count != c->geometry.tri_materials || d->materials_count != c->geometry.materials) {
         (void)fail("geometry arrays changed size since the last upload");
@@ -725,19 +655,13 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
             return fail("%s", why.c_str());
         }
     }
-    {
-        size_t quads = 0;
-        for (int lod = 0; lod < d->env.qtree_levels; ++lod) {
-            quads += size_t(1) << (2 * (d->env.qtree_levels - 1 - lod));
-        }
-        if (size_t(d->env_qtree_count) != quads * 4) {
-            return fail("env_qtree holds %u floats, %d levels need %zu", d->env_qtree_count, d->env.qtree_levels, quads * 4);
-        }
-        for (const uint32_t handle : {d->env.env_map, d->env.back_map}) {
-            if (handle != 0xffffffffu &&
-                ((handle >> 28) >= 8u || uint64_t(c->tex_table[handle >> 28]) + (handle & 0x00ffffffu) >= c->textures_count)) {
-                return fail("environment map handle outside the texture table on the device");
-            }
+    if (check_env_qtree_size(d)) {
+        return 1;
+    }
+    for (const uint32_t handle : {d->env.env_map, d->env.back_map}) {
+        if (handle != 0xffffffffu &&
+            ((handle >> 28) >= 8u || uint64_t(c->tex_table[handle >> 28]) + (handle & 0x00ffffffu) >= c->textures_count)) {
+            return fail("environment map handle outside the texture table on the device");
         }
     }
     rayhip_update::Plan up;
@@ -765,7 +689,7 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
     if (const int rc = rebuild_top_level(c, up, tlas_root, root_box)) {
         return rc;
     }
-    UPLOAD_TRACE("top level built")
+    trace("top level built");
     if (upload(c, c->mesh_instances, mis.data(), mis.size() * sizeof(rayhip_mesh_instance)) ||
         (c->wide && upload(c, c->blas_root4, root4.data(), root4.size() * sizeof(uint32_t)))) {
         return 1;
@@ -789,7 +713,7 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
     }
     refresh_scene_view(c, d, tlas_root, root_box, uint32_t(live.size()));
     c->refit.live = live, c->refit.instances = mis; // (what a later rayhip_scene_update_vertices rebuilds the top level over)
-    UPLOAD_TRACE("instances updated")
+    trace("instances updated");
     return 0;
 }
 
@@ -857,523 +781,6 @@ int rayhip_scene_update_instances_blob(rayhip_ctx *c, const void *blob, size_t s
     }
     return rayhip_scene_update_instances(c, &d);
 }
-
-// the stamps of the vertex updates (RAYHIP_TRACE_UPLOAD): a stamp waits for the device first, so that the phases can be told apart (only when tracing)
-#define VERTEX_TRACE_AS(who, msg)                                                                                      \
-    if (trace) {                                                                                                       \
-        HIP_TRY(hipStreamSynchronize(c->stream));                                                                      \
-        fprintf(stderr, who ": %9.3f ms  %s\n",                                                                        \
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), msg);         \
-    }
-#define VERTEX_TRACE(msg) VERTEX_TRACE_AS("rayhip_scene_update_vertices", msg)
-
-static int refit_after_vertices(rayhip_ctx *c, bool trace, std::chrono::steady_clock::time_point t0);
-static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, bool trace, std::chrono::steady_clock::time_point t0);
-
-// ---- vertex update: meshes deform in place, the trees are kept and refitted on the device ----------------------------------------
-// Kept: tree topology, triangle order (tri_indices), materials, lights, instances.  Recomputed from the new positions, all in stream
-// order: the triangle records (k_refit_tris), the child boxes of every bottom-level BVH2 node (k_refit_level, one launch per height),
-// the per-triangle vertex table (k_fill_tri_verts), the 4-wide collapse over the same root list, the instance boxes (host, from the root
-// nodes read back) and the top level (the path of rayhip_scene_update_instances).  refit.h / refit.hip.h.
-int rayhip_scene_update_vertices(rayhip_ctx *c, uint32_t first_vertex, uint32_t count, const rayhip_vertex *vertices) {
-    if (use_device(c)) {
-        return 1;
-    }
-    rayhip_ctx::Refit &r = c->refit;
-    if (!c->have_scene) {
-        (void)fail("rayhip_scene_update_vertices before rayhip_scene_upload");
-        return 2;
-    }
-    if (c->wide == 8) {
-        (void)fail("rayhip_scene_update_vertices: the context walks the 8-wide tree, whose builder runs on the host only");
-        return 2;
-    }
-    if (r.levels_rc != 0) {
-        (void)fail("rayhip_scene_update_vertices: a bottom-level tree is higher than %u levels", rayhip_refit::MAX_LEVELS);
-        return 2;
-    }
-    if (uint64_t(first_vertex) + count > c->geometry.vertices || (count != 0 && vertices == nullptr)) {
-        return fail("rayhip_scene_update_vertices: vertices [%u, %u + %u) are outside the %u of the uploaded scene", first_vertex, first_vertex, count,
-                    c->geometry.vertices);
-    }
-    for (uint32_t i = 0; i < count; ++i) {
-        if (r.vertex_used[first_vertex + i] && (!std::isfinite(vertices[i].p[0]) || !std::isfinite(vertices[i].p[1]) || !std::isfinite(vertices[i].p[2]))) {
-            return fail("rayhip_scene_update_vertices: the position of vertex %u is not finite", first_vertex + i);
-        }
-    }
-    for (const auto &kept : r.light_vertices) { // (ascending; few)
-        if (c->light_refit.on) {
-            break; // (rayhip_scene_refit_lights: the lights follow their vertices)
-        }
-        if (kept.first >= first_vertex && kept.first - first_vertex < count &&
-            memcmp(&vertices[kept.first - first_vertex], &kept.second, sizeof(rayhip_vertex)) != 0) {
-            (void)fail("rayhip_scene_update_vertices: vertex %u belongs to a triangle light; lights are not rebuilt by this call", kept.first);
-            return 2;
-        }
-    }
-    const bool trace = getenv("RAYHIP_TRACE_UPLOAD") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
-    VERTEX_TRACE("begin")
-    if (count) {
-        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + first_vertex, vertices, size_t(count) * sizeof(rayhip_vertex), hipMemcpyHostToDevice, c->stream));
-    }
-    VERTEX_TRACE("vertices copied")
-    return refit_after_vertices(c, trace, t0);
-}
-
-// everything a vertex update recomputes once the new vertices are in c->vertices (in stream order behind them); `t0`: the start of
-// the call, for the stamps
-static int refit_after_vertices(rayhip_ctx *c, const bool trace, const std::chrono::steady_clock::time_point t0) {
-    rayhip_ctx::Refit &r = c->refit;
-    hipStream_t s = c->stream;
-    const uint32_t n_tris = c->geometry.vtx_indices / 3;
-    uint32_t *d_degenerate = r.scratch.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(d_degenerate, 0, 2 * sizeof(uint32_t), s)); // ([1]: triangle LIGHTS without area, when the lights are refitted)
-    if (r.entries) {
-        rayhip_refit::k_refit_tris<<<(r.entries + 255) / 256, 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(),
-                                                                           n_tris, c->tri_indices.as<uint32_t>(), r.first_entry.as<uint32_t>(), r.entries,
-                                                                           c->tris.as<float4>(), c->tri_pitch, d_degenerate);
-        HIP_TRY(hipGetLastError());
-    }
-    VERTEX_TRACE("triangle records")
-    for (size_t h = 1; h < r.level_offset.size(); ++h) {
-        const uint32_t n = r.level_offset[h] - r.level_offset[h - 1];
-        rayhip_refit::k_refit_level<<<(n + 255) / 256, 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), r.level_nodes.as<uint32_t>() + r.level_offset[h - 1], n,
-                                                                    c->tri_indices.as<uint32_t>(), c->vtx_indices.as<uint32_t>(), c->vertices.as<rayhip_vertex>());
-        HIP_TRY(hipGetLastError());
-    }
-    VERTEX_TRACE("boxes refitted")
-    if (n_tris) {
-        k_fill_tri_verts<<<(n_tris + 255) / 256, 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(), n_tris,
-                                                              c->tri_materials.as<rayhip_tri_mat_data>(), c->geometry.tri_materials, c->tri_verts.as<float4>(),
-                                                              c->tri_bitangents.as<float4>());
-        HIP_TRY(hipGetLastError());
-    }
-    VERTEX_TRACE("tri_verts done")
-    if (c->light_refit.on) { // rayhip_scene_refit_lights: the lights follow the vertices just written
-        if (refit_lights(c, d_degenerate + 1, trace, t0)) {
-            return 1;
-        }
-        HIP_TRY(hipMemcpyAsync(&c->light_refit.degenerate, d_degenerate + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    }
-    // the root node of every mesh in use -> the host; the count of triangles without area comes with them
-    std::vector<rayhip_bvh2_node> root_nodes(r.roots.size());
-    {
-        uint32_t *d_which = reinterpret_cast<uint32_t *>(r.scratch.as<uint8_t>() + 256);
-        rayhip_bvh2_node *d_roots = reinterpret_cast<rayhip_bvh2_node *>(r.scratch.as<uint8_t>() + 256 + ((r.roots.size() * sizeof(uint32_t) + 63) & ~size_t(63)));
-        if (!r.roots.empty()) {
-            HIP_TRY(hipMemcpyAsync(d_which, r.roots.data(), r.roots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            rayhip_refit::k_gather_nodes<<<unsigned((r.roots.size() + 255) / 256), 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), d_which, uint32_t(r.roots.size()),
-                                                                                               d_roots);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(root_nodes.data(), d_roots, r.roots.size() * sizeof(rayhip_bvh2_node), hipMemcpyDeviceToHost, s));
-        }
-        HIP_TRY(hipMemcpyAsync(&r.degenerate, d_degenerate, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    }
-    // the 4-wide trees over the boxes just written: the same root list as at upload, so the wide node of roots[k] is k again
-    if (c->wide == 4 && !r.roots.empty()) {
-        uint32_t n_wide = 0;
-        std::string why;
-        bool unquantisable = false;
-        if (!rayhip_bvh4::build_device(s, c->nodes.as<rayhip_bvh2_node>(), c->nodes_used, r.roots, c->nodes4.as<Bvh4Node>(), n_wide, why, &unquantisable)) {
-            if (!unquantisable) {
-                return fail("4-wide collapse failed: %s", why.c_str());
-            }
-            // a box the grid cannot hold: the kernels walk the BVH2 from here on, as after an upload of such a scene
-            c->wide = 0, c->small_scene = false;
-            c->sc.nodes4 = nullptr, c->sc.blas_root4 = nullptr;
-            for (auto &ref : c->mesh_refs) {
-                ref.second.root4 = 0;
-            }
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    VERTEX_TRACE(c->wide == 4 ? "bvh4 built" : "no wide BLAS")
-    if (trace) {
-        fprintf(stderr, "rayhip_scene_update_vertices: %u triangles without area\n", r.degenerate);
-        if (c->light_refit.on) {
-            fprintf(stderr, "rayhip_scene_update_vertices: %u triangle lights without area\n", c->light_refit.degenerate);
-        }
-    }
-    // the top level over the new instance boxes: the live slots and the instance array of the last upload / instance update.  The leaf
-    // numbering is the one scene_update.h: plan documents (a leaf names the slot the host's leaf named); the box of a slot is made from
-    // that slot's own mesh and transform, which is what the walk follows the leaf to.
-    rayhip_update::Plan up;
-    up.live = r.live, up.instances = r.instances;
-    up.root4.assign(up.instances.size(), 0u);
-    for (const uint32_t mi : up.live) {
-        const auto it = mi < up.instances.size() ? r.ordinal_of_root.find(up.instances[mi].node_index) : r.ordinal_of_root.end();
-        if (it == r.ordinal_of_root.end()) {
-            return fail("rayhip_scene_update_vertices: instance %u has no tree on the device", mi);
-        }
-        up.root4[mi] = c->wide == 4 ? it->second : 0u;
-        up.boxes.push_back(rayhip_rebuild::transform_box(rayhip_rebuild::node_box(root_nodes[it->second]), up.instances[mi].xform));
-    }
-    if (c->wide == 4) {
-        for (auto &ref : c->mesh_refs) {
-            const auto it = r.ordinal_of_root.find(ref.second.node_index);
-            if (it != r.ordinal_of_root.end()) {
-                ref.second.root4 = it->second;
-            }
-        }
-        if (upload(c, c->blas_root4, up.root4.data(), up.root4.size() * sizeof(uint32_t))) {
-            return 1;
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    uint32_t tlas_root = 0xffffffffu;
-    rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
-    if (const int rc = rebuild_top_level(c, up, tlas_root, root_box)) {
-        return rc == 2 ? fail("rayhip_scene_update_vertices: %s", g_err.c_str()) : rc; // (the arrays are the new ones already: an error)
-    }
-    refresh_top_level_view(c, tlas_root, root_box, uint32_t(up.live.size()));
-    VERTEX_TRACE("top level built")
-    return 0;
-}
-
-// ---- the switch: vertex updates and poses may move triangle lights (light_refit.h) --------------------------------------------------
-// A property of the context.  Whichever comes second of this call and the upload prepares the tables (prepare_light_refit): here from
-// the light arrays read back, which hold the topology and the fluxes of the lights that are no triangles whatever refits ran before.
-int rayhip_scene_refit_lights(rayhip_ctx *c, int on) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    rayhip_ctx::LightRefit &lr = c->light_refit;
-    if (!on) {
-        if (!lr.on) {
-            return 0;
-        }
-        for (const rayhip_ctx::Skin &k : c->skins) {
-            for (const auto &kept : c->refit.light_vertices) {
-                if (k.live && kept.first >= k.first && kept.first - k.first < k.count) {
-                    return fail("rayhip_scene_refit_lights: skin %d covers vertex %u of a triangle light; destroy it first", k.id, kept.first);
-                }
-            }
-        }
-        // from here on a changed light vertex is refused again: "changed" against what the lights on the device describe NOW
-        if (c->have_scene && !c->refit.light_vertices.empty()) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            std::vector<rayhip_vertex> now(c->geometry.vertices);
-            HIP_TRY(hipMemcpy(now.data(), c->vertices.p, now.size() * sizeof(rayhip_vertex), hipMemcpyDeviceToHost));
-            for (auto &kept : c->refit.light_vertices) {
-                if (kept.first < now.size()) {
-                    kept.second = now[kept.first];
-                }
-            }
-            if (upload_vertex_checks(c, false)) {
-                return 1;
-            }
-        }
-        lr.on = false;
-        return 0;
-    }
-    if (lr.on) {
-        return 0;
-    }
-    if (c->have_scene && !lr.ready) {
-        // everything the tables are made from, read back: the tree is the one the last upload or instance update brought (no refit ran
-        // since: the switch was off).  The pose it describes is that of the KEPT light vertices -- taken from the host's arrays with the
-        // tree, re-taken from the device when the switch went off, and unchangeable while it is off -- not necessarily what the vertex
-        // array holds: an instance update that came while the switch was off left a deformed emitter where it was
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::vector<rayhip_light> lights(lr.lights_count);
-        std::vector<rayhip_light_cwbvh_node> nodes(lr.nodes_count);
-        std::vector<uint32_t> li(lr.li_count), vi(c->geometry.vtx_indices);
-        std::vector<rayhip_vertex> vertices(c->geometry.vertices);
-        std::vector<rayhip_mesh_instance> instances(c->instances_count);
-        auto back = [&](void *dst, const DevBuf &src, const size_t bytes) {
-            return bytes == 0 || hipMemcpy(dst, src.p, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-        };
-        if (!back(lights.data(), c->lights, lights.size() * sizeof(rayhip_light)) || !back(nodes.data(), c->light_cwnodes, nodes.size() * sizeof(rayhip_light_cwbvh_node)) ||
-            !back(li.data(), c->li_indices, li.size() * sizeof(uint32_t)) || !back(vi.data(), c->vtx_indices, vi.size() * sizeof(uint32_t)) ||
-            !back(vertices.data(), c->vertices, vertices.size() * sizeof(rayhip_vertex)) ||
-            !back(instances.data(), c->mesh_instances, instances.size() * sizeof(rayhip_mesh_instance))) {
-            return fail("rayhip_scene_refit_lights: reading the scene back failed");
-        }
-        for (const auto &kept : c->refit.light_vertices) {
-            if (kept.first < vertices.size()) {
-                vertices[kept.first] = kept.second;
-            }
-        }
-        rayhip_scene_desc d = {};
-        d.lights = lights.data(), d.lights_count = lr.lights_count, d.light_cwnodes = nodes.data(), d.light_cwnodes_count = lr.nodes_count;
-        d.li_indices = li.data(), d.li_indices_count = lr.li_count, d.vtx_indices = vi.data(), d.vtx_indices_count = uint32_t(vi.size());
-        d.vertices = vertices.data(), d.vertices_count = uint32_t(vertices.size());
-        d.mesh_instances = instances.data(), d.mesh_instances_count = uint32_t(instances.size());
-        if (prepare_light_refit(c, &d)) {
-            return 1;
-        }
-    }
-    lr.on = true;
-    return 0;
-}
-
-int rayhip_scene_update_vertices_blob(rayhip_ctx *c, const void *blob, size_t size) {
-    rayhip_scene_desc d;
-    rayhip_camera cam;
-    const float *ft = nullptr;
-    int ftn = 0;
-    std::string err;
-    if (!rayhip_blob::deserialize(blob, size, d, cam, &ft, &ftn, err, nullptr)) {
-        return fail("%s", err.c_str());
-    }
-    if (c && c->have_scene && (d.vertices_count != c->geometry.vertices || d.vtx_indices_count != c->geometry.vtx_indices)) {
-        return fail("rayhip_scene_update_vertices_blob: the blob holds %u vertices / %u indices, the uploaded scene %u / %u", d.vertices_count,
-                    d.vtx_indices_count, c->geometry.vertices, c->geometry.vtx_indices);
-    }
-    return rayhip_scene_update_vertices(c, 0, d.vertices_count, d.vertices);
-}
-
-// ---- vertex updates whose vertices never pass through the host: skins, and arrays the caller holds on the device -------------------
-// Both run a kernel over the new vertices BEFORE the vertex array is written (posed into a staging array / checked where the caller has
-// them), read its counters back, and only then copy device to device and refit: a refused update has touched nothing.  skin.h, skin.hip.h.
-
-// 0 = the context can take a vertex update, 2 = it needs rayhip_scene_upload (the conditions of rayhip_scene_update_vertices)
-static int vertex_update_possible(rayhip_ctx *c, const char *who) {
-    if (!c->have_scene) {
-        (void)fail("%s before rayhip_scene_upload", who);
-        return 2;
-    }
-    if (c->wide == 8) {
-        (void)fail("%s: the context walks the 8-wide tree, whose builder runs on the host only", who);
-        return 2;
-    }
-    if (c->refit.levels_rc != 0 || c->refit.vertex_used.size() != c->geometry.vertices) {
-        (void)fail("%s: a bottom-level tree is higher than %u levels", who, rayhip_refit::MAX_LEVELS);
-        return 2;
-    }
-    return 0;
-}
-
-// the light refit behind the geometry refit of a vertex update, in stream order (light_refit.hip.h): the triangle lights' corners
-// and summaries, then the tree, one launch per height.  `d_degenerate`: where the triangles without area are counted.
-static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, const bool trace, const std::chrono::steady_clock::time_point t0) {
-    rayhip_ctx::LightRefit &lr = c->light_refit;
-    if (!lr.ready) {
-        return fail("rayhip_scene_refit_lights is on, but its tables are not prepared");
-    }
-    hipStream_t s = c->stream;
-    if (lr.li_count) {
-        rayhip_light_refit::k_refit_tri_lights<<<(lr.li_count + 255) / 256, 256, 0, s>>>(
-            c->lights.as<rayhip_light>(), lr.lights_count, c->li_indices.as<uint32_t>(), lr.li_count, c->mesh_instances.as<rayhip_mesh_instance>(), c->instances_count,
-            c->vtx_indices.as<uint32_t>(), c->geometry.vtx_indices, c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->light_tri_geom.as<float4>(),
-            lr.leaf.as<rayhip_light_refit::Summary>(), d_degenerate);
-        HIP_TRY(hipGetLastError());
-    }
-    VERTEX_TRACE("light corners")
-    for (size_t h = 0; h + 1 < lr.level_offset.size(); ++h) {
-        const uint32_t n = lr.level_offset[h + 1] - lr.level_offset[h];
-        if (n == 0) {
-            continue;
-        }
-        rayhip_light_refit::k_refit_light_level<<<unsigned((size_t(n) * 8 + 255) / 256), 256, 0, s>>>(
-            c->light_cwnodes.as<rayhip_light_cwbvh_node>(), lr.level_nodes.as<uint32_t>() + lr.level_offset[h], n, c->lights.as<rayhip_light>(),
-            lr.leaf.as<rayhip_light_refit::Summary>(), lr.node_summary.as<rayhip_light_refit::Summary>(), c->light_children.as<float4>(),
-            lr.slot_scale.as<float>());
-        HIP_TRY(hipGetLastError());
-    }
-    VERTEX_TRACE("light tree refitted")
-    return 0;
-}
-
-int rayhip_skin_create(rayhip_ctx *c, const rayhip_skin_desc *d, int *out_skin) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (!d || !out_skin || !d->bone_indices || !d->bone_weights) {
-        return fail("rayhip_skin_create: a null pointer");
-    }
-    if (const int rc = vertex_update_possible(c, "rayhip_skin_create")) {
-        return rc;
-    }
-    if (d->count == 0 || uint64_t(d->first_vertex) + d->count > c->geometry.vertices) {
-        return fail("rayhip_skin_create: vertices [%u, %u + %u) are outside the %u of the uploaded scene", d->first_vertex, d->first_vertex, d->count,
-                    c->geometry.vertices);
-    }
-    if (d->bones_count == 0 || d->bones_count > 65536u) {
-        return fail("rayhip_skin_create: %u bones (bone indices are 16-bit)", d->bones_count);
-    }
-    int slot = -1;
-    for (int k = int(rayhip_skin::MAX_SKINS) - 1; k >= 0; --k) {
-        const rayhip_ctx::Skin &o = c->skins[k];
-        if (!o.live) {
-            slot = k;
-        } else if (d->first_vertex < o.first + o.count && o.first < d->first_vertex + d->count) {
-            return fail("rayhip_skin_create: vertices [%u, %u + %u) overlap skin %d", d->first_vertex, d->first_vertex, d->count, o.id);
-        }
-    }
-    if (slot < 0) {
-        return fail("rayhip_skin_create: %u skins are live already", rayhip_skin::MAX_SKINS);
-    }
-    {
-        uint32_t where = 0;
-        if (const int bad = rayhip_skin::validate_influences(d->bone_indices, d->bone_weights, d->count, d->bones_count, where)) {
-            return bad == 1 ? fail("rayhip_skin_create: vertex %u names a bone outside the palette of %u", d->first_vertex + where, d->bones_count)
-                            : fail("rayhip_skin_create: a weight of vertex %u is negative or not finite", d->first_vertex + where);
-        }
-    }
-    for (const auto &kept : c->refit.light_vertices) {
-        if (c->light_refit.on) {
-            break; // (rayhip_scene_refit_lights: the lights follow their vertices)
-        }
-        if (kept.first >= d->first_vertex && kept.first - d->first_vertex < d->count) {
-            (void)fail("rayhip_skin_create: vertex %u belongs to a triangle light; lights are not rebuilt by a pose", kept.first);
-            return 2;
-        }
-    }
-    rayhip_ctx::Skin &k = c->skins[slot];
-    const size_t n = d->count;
-    if (k.rest.alloc(n * sizeof(rayhip_vertex)) || upload(c, k.indices, d->bone_indices, n * 4 * sizeof(uint16_t)) ||
-        upload(c, k.weights, d->bone_weights, n * 4 * sizeof(float))) {
-        return 1;
-    }
-    HIP_TRY(hipMemcpyAsync(k.rest.p, d->rest ? static_cast<const void *>(d->rest) : static_cast<const void *>(c->vertices.as<rayhip_vertex>() + d->first_vertex),
-                           n * sizeof(rayhip_vertex), d->rest ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream)); // the caller's arrays may go away after this call
-    c->skin_serial = (c->skin_serial % 0x7ffffffu) + 1; // (1 .. 2^27 - 1: the handle stays a positive int, and is never a return code)
-    k.live = true, k.id = int(c->skin_serial << 4) | slot, k.first = d->first_vertex, k.count = d->count, k.bones_count = d->bones_count;
-    *out_skin = k.id;
-    return 0;
-}
-
-int rayhip_skin_destroy(rayhip_ctx *c, int skin) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (!c->skin_of(skin)) {
-        (void)fail("rayhip_skin_destroy: skin %d is not live", skin);
-        return 2;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    rayhip_ctx::Skin &k = *c->skin_of(skin);
-    k.live = false;
-    k.rest.release(), k.indices.release(), k.weights.release();
-    return 0;
-}
-
-int rayhip_scene_pose_skins(rayhip_ctx *c, int n, const int *skins, const float *const *palettes) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (n < 0 || n > int(rayhip_skin::MAX_SKINS) || (n > 0 && (!skins || !palettes))) {
-        return fail("rayhip_scene_pose_skins: bad arguments");
-    }
-    if (const int rc = vertex_update_possible(c, "rayhip_scene_pose_skins")) {
-        return rc;
-    }
-    size_t stage_vertices = 0, palette_floats = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!c->skin_of(skins[i])) {
-            (void)fail("rayhip_scene_pose_skins: skin %d is not live", skins[i]);
-            return 2;
-        }
-        if (!palettes[i]) {
-            return fail("rayhip_scene_pose_skins: no palette for skin %d", skins[i]);
-        }
-        for (int j = 0; j < i; ++j) {
-            if (skins[j] == skins[i]) {
-                return fail("rayhip_scene_pose_skins: skin %d is named twice", skins[i]);
-            }
-        }
-        stage_vertices += c->skin_of(skins[i])->count, palette_floats += size_t(c->skin_of(skins[i])->bones_count) * 12;
-    }
-    if (n == 0) {
-        return 0;
-    }
-    const bool trace = getenv("RAYHIP_TRACE_UPLOAD") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
-    VERTEX_TRACE_AS("rayhip_scene_pose_skins", "begin")
-    hipStream_t s = c->stream;
-    if (c->skin_stage.alloc(stage_vertices * sizeof(rayhip_vertex)) || c->skin_palettes.alloc(palette_floats * sizeof(float)) ||
-        c->skin_counters.alloc(2 * sizeof(uint32_t))) {
-        return 1;
-    }
-    uint32_t *d_counters = c->skin_counters.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
-    {
-        size_t at_vertex = 0, at_float = 0;
-        for (int i = 0; i < n; ++i) {
-            const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
-            float *d_palette = c->skin_palettes.as<float>() + at_float;
-            HIP_TRY(hipMemcpyAsync(d_palette, palettes[i], size_t(k.bones_count) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
-            rayhip_skin::k_skin_vertices<<<(k.count + 255) / 256, 256, 0, s>>>(k.rest.as<rayhip_vertex>(), k.indices.as<uint16_t>(), k.weights.as<float>(), k.count,
-                                                                              d_palette, k.bones_count, c->refit.d_vertex_used.as<uint8_t>() + k.first,
-                                                                              c->skin_stage.as<rayhip_vertex>() + at_vertex, d_counters);
-            HIP_TRY(hipGetLastError());
-            at_vertex += k.count, at_float += size_t(k.bones_count) * 12;
-        }
-    }
-    uint32_t counters[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s)); // (the caller's palettes may go away after this)
-    VERTEX_TRACE_AS("rayhip_scene_pose_skins", "vertices posed")
-    if (counters[0] != 0) {
-        return fail("rayhip_scene_pose_skins: the posed position of %u vertices is not finite", counters[0]);
-    }
-    {
-        size_t at_vertex = 0;
-        for (int i = 0; i < n; ++i) {
-            const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
-            HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + k.first, c->skin_stage.as<rayhip_vertex>() + at_vertex, size_t(k.count) * sizeof(rayhip_vertex),
-                                   hipMemcpyDeviceToDevice, s));
-            at_vertex += k.count;
-        }
-    }
-    VERTEX_TRACE_AS("rayhip_scene_pose_skins", "vertices copied")
-    return refit_after_vertices(c, trace, t0);
-}
-
-int rayhip_scene_update_vertices_device(rayhip_ctx *c, uint32_t first_vertex, uint32_t count, const rayhip_vertex *device_vertices) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (const int rc = vertex_update_possible(c, "rayhip_scene_update_vertices_device")) {
-        return rc;
-    }
-    if (uint64_t(first_vertex) + count > c->geometry.vertices || (count != 0 && device_vertices == nullptr)) {
-        return fail("rayhip_scene_update_vertices_device: vertices [%u, %u + %u) are outside the %u of the uploaded scene", first_vertex, first_vertex, count,
-                    c->geometry.vertices);
-    }
-    const bool trace = getenv("RAYHIP_TRACE_UPLOAD") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
-    VERTEX_TRACE_AS("rayhip_scene_update_vertices_device", "begin")
-    hipStream_t s = c->stream;
-    rayhip_ctx::Refit &r = c->refit;
-    if (c->skin_counters.alloc(2 * sizeof(uint32_t))) {
-        return 1;
-    }
-    uint32_t *d_counters = c->skin_counters.as<uint32_t>();
-    uint32_t counters[2] = {0, 0};
-    const uint32_t n_lights = c->light_refit.on ? 0u : uint32_t(r.light_vertices.size()); // (refitted lights may move: nothing to compare)
-    if (count) {
-        HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
-        rayhip_skin::k_check_vertices<<<(std::max(count, n_lights) + 255) / 256, 256, 0, s>>>(device_vertices, first_vertex, count, r.d_vertex_used.as<uint8_t>(),
-                                                                                             r.d_light_index.as<uint32_t>(), r.d_light_vertices.as<rayhip_vertex>(),
-                                                                                             n_lights, d_counters);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    VERTEX_TRACE_AS("rayhip_scene_update_vertices_device", "vertices checked")
-    if (counters[0] != 0) {
-        return fail("rayhip_scene_update_vertices_device: the position of %u vertices is not finite", counters[0]);
-    }
-    if (counters[1] != 0) {
-        (void)fail("rayhip_scene_update_vertices_device: %u vertices of triangle lights changed; lights are not rebuilt by this call", counters[1]);
-        return 2;
-    }
-    if (count) {
-        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + first_vertex, device_vertices, size_t(count) * sizeof(rayhip_vertex), hipMemcpyDeviceToDevice, s));
-    }
-    VERTEX_TRACE_AS("rayhip_scene_update_vertices_device", "vertices copied")
-    return refit_after_vertices(c, trace, t0);
-}
-
-#undef VERTEX_TRACE
-#undef VERTEX_TRACE_AS
 
 // test hook: a device array of the acceleration structure -> the host
 int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_bytes, size_t *out_bytes) {

@@ -1,4 +1,4 @@
-// refit.hip.h -- the device side of a vertex update (rayhip_scene_update_vertices, rayhip_upload.hip.h): the element functions
+// refit.hip.h -- the device side of a vertex update (rayhip_scene_update_vertices, rayhip_deform.hip.h): the element functions
 // of refit.h, one lane per item.  The tree is refitted with ONE LAUNCH PER HEIGHT LEVEL: a launch reads what the launches
 // before it wrote, and the kernel boundary is what makes that visible -- no flags between waves, no fences to get wrong.
 #pragma once

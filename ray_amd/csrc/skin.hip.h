@@ -1,4 +1,4 @@
-// skin.hip.h -- the device side of skinning (rayhip_scene_pose_skins, rayhip_scene_update_vertices_device; rayhip_upload.hip.h): the
+// skin.hip.h -- the device side of skinning (rayhip_scene_pose_skins, rayhip_scene_update_vertices_device; rayhip_deform.hip.h): the
 // element functions of skin.h, one lane per vertex.  Both kernels only READ what a render pass reads: the posed vertices go to a
 // staging array and the findings to counters, so a refused update has touched nothing.
 #pragma once
