@@ -399,6 +399,11 @@ RAYHIP_API int rayhip_scene_bvh_width(rayhip_ctx *ctx);
  * BLAS; RAYHIP_REFILL selects).  All forms find the same hits bit for bit; this is what bench.py names in its roofline block. */
 RAYHIP_API int rayhip_closest_hit_form(rayhip_ctx *ctx);
 
+/* 1 = the persistent walks (k_trace_closest_refill in both forms, k_trace_shadow_refill) run in their direct-entry form for the uploaded
+ * scene: its top level holds ONE instance over the 4-wide BLAS, which the kernels take from their arguments instead of walking the top
+ * level for every ray (same hits bit for bit; RAYHIP_DIRECT_ENTRY=0 turns it off); 0 = they walk the top level. */
+RAYHIP_API int rayhip_direct_entry(rayhip_ctx *ctx);
+
 /* Same upload from a serialised scene (ray_amd/csrc/scene_blob.h; written by the reference-side SceneHIP or by
  * tests/golden/make_fixtures.py): uploads the arrays AND the filter table stored in the blob and returns the
  * camera stored with it.  `blob` must be 16-byte aligned. */

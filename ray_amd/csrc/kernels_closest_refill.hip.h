@@ -56,7 +56,30 @@
 #ifndef RT_REFILL_RUN
 #define RT_REFILL_RUN 1
 #endif
-template <int WIDE, int MIN_WAIT = RT_REFILL_MIN>
+// ---- direct entry (DIRECT; scenes whose top level holds ONE instance, 4-wide tree: rayhip_ctx::direct_scene, RAYHIP_DIRECT_ENTRY) --------------
+// Such a top level is a root whose two links are the same leaf word, the second one behind a point box at the origin (rayhip_upload.hip.h:
+// count_top_level_instances).  Walking it costs every ray a node fetch (4 x 16 bytes), two box tests, a per-lane fetch of the instance record
+// and of blas_root4[mi], a second stack entry and a second pop -- two rounds of service part C and three of the service part's four dependent
+// memory round trips -- for values that are the same for every ray of the launch.  In this form the instance arrives in the kernel arguments
+// (SceneView::direct: scalar loads), begin_round enters it at once, and the lane state has no top level: the pop that takes the sentinel ends
+// the round (lvl TLAS + the sentinel in `cur` remain the mark of a finished round, so part D reads as before), part C and the second pop of
+// leave_blas are not compiled in.  Inside the instance every ray runs the same code on the same values.
+// The hits are the same bits as the generic form's:
+//   (a) the top-level box test only culls, and its box bounds the instance: a ray it rejects is rejected by the child boxes of the BLAS
+//       root or finds no triangle nearer than h.t -- the round ends with `res` false and `h` untouched either way;
+//   (b) a ray that also passes the point box of the duplicate link walks the same instance a second time in the generic form.  That walk
+//       tests the same triangles against the h.t the first one left; a hit at equal t is not closer (rt_isect.h compares with <), so
+//       (obj, prim, t, u, v) and `res` stay what the first walk made them.
+// all_solid scenes: `ro` never moves (no transparency round), the finish step's  h.t += length(o0 - ro)  adds +0.0f to a t that is positive
+// or MAX_DIST, and the reload of the origin is skipped.
+// RESULTS (profiles/direct_entry; parent against this form in one session, bit-identical frames): K2 secondary 521.1 -> 506.7 ms per traced run, K2
+// primary 90.3 -> 84.4, K3 544.9 -> 531.0; headline 779.9 .. 782.1 -> 797.5 .. 799.1 Msamples/s.
+// Threshold of the direct-entry instantiation: its service round is the cheaper one, but the optimum did not move -- 16 / 24 / 32 / 40 lanes
+// waiting: 521.7 / 512.2 / 507.3 / 506.7 ms per traced run
+#ifndef RT_REFILL_MIN_DIRECT
+#define RT_REFILL_MIN_DIRECT 40
+#endif
+template <int WIDE, int MIN_WAIT = RT_REFILL_MIN, bool DIRECT = false>
 __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_refill(const SceneView sc, const TraceParams tp, const RaySoA rays,
                                                                const HitSoA hits, const RayQueue queue, const int init_hits,
                                                                uint32_t *__restrict__ stack_spill, const Layering layers,
@@ -98,6 +121,21 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
         t_val = h.t;
         res = false;
         size = 0;
+        if (DIRECT) { // ... + the entry of the one instance (what part C does at its leaf)
+            tos = BVH4_SENTINEL;
+            if ((sc.direct.ray_visibility & ray_flags) != 0) {
+                o = transform_point(ro, sc.direct.inv_xform);
+                d = transform_direction(rd, sc.direct.inv_xform);
+                inv_d = safe_invert(d);
+                st.write_at(size++, BVH4_SENTINEL);
+                cur = sc.direct.root;
+                lvl = (cur == BVH4_SENTINEL) ? TLAS : BLAS; // (a BLAS whose root is the sentinel: nothing to walk)
+            } else { // the round is over with no hit
+                cur = BVH4_SENTINEL;
+                lvl = TLAS;
+            }
+            return;
+        }
         st.write_at(size++, BVH4_SENTINEL);
         tos = BVH4_SENTINEL;
         cur = tp.root_index;
@@ -117,7 +155,9 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
             }
         } else if (lvl == BLAS && cur == BVH4_SENTINEL) {
             lvl = TLAS;
-            pop();
+            if (!DIRECT) {
+                pop();
+            }
         }
     };
     auto pop8 = [&]() {
@@ -174,7 +214,7 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
                 if (at_leaf) {
                     const uint32_t word = WIDE == 8 ? bvh8_take_leaf(tri_base, l0, l1) : cur;
                     const int tri_start = int(word & BVH2_PRIM_INDEX_BITS), tri_end = int(tri_start + ((word & BVH2_PRIM_COUNT_BITS) >> 29) + 1);
-                    const bool hit = intersect_tris_closest(o, d, tri_table(sc), tri_start, tri_end, int(mi_index), h);
+                    const bool hit = intersect_tris_closest(o, d, tri_table(sc), tri_start, tri_end, DIRECT ? int(sc.direct.mi) : int(mi_index), h);
                     res |= hit;
                     if (WIDE == 8) {
                         if ((l0 | l1) == 0u && (cur_bits >> 8) == 0u) {
@@ -232,8 +272,10 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
                 if (again) {
                     begin_round();
                 } else {
-                    const float4 o0 = rays.o_pdf[slot];
-                    h.t += length(f3{o0.x, o0.y, o0.z} - ro);
+                    if (!(DIRECT && sc.all_solid != 0u)) { // (direct entry, every side solid: `ro` is still the ray's origin, the addend +0.0f)
+                        const float4 o0 = rays.o_pdf[slot];
+                        h.t += length(f3{o0.x, o0.y, o0.z} - ro);
+                    }
                     store_hit(hits, slot, h);
                     lvl = IDLE;
                 }
@@ -281,6 +323,9 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
         }
 
         // ---- service part, C: TLAS steps until every lane is inside an instance or through with its TLAS walk
+        if (DIRECT) {
+            continue; // (no top level: begin_round entered the instance)
+        }
         for (;;) {
             const bool in_c = (lvl == TLAS) && (cur != BVH4_SENTINEL);
             if (__builtin_amdgcn_readfirstlane(int(__ballot(in_c) == 0ull))) {

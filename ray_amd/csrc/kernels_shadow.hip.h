@@ -67,7 +67,12 @@ __global__ void __launch_bounds__(WAVE, MINW) k_trace_shadow(const SceneView sc,
 #ifndef RT_SHADOW_RUN
 #define RT_SHADOW_RUN 4
 #endif
-template <int MIN_WAIT = RT_SHADOW_REFILL_MIN>
+// DIRECT: the direct-entry form for scenes whose top level holds one instance (kernels_closest_refill.hip.h has the argument): begin_segment
+// enters the instance from the kernel arguments, no top-level state, no part C.
+#ifndef RT_SHADOW_REFILL_MIN_DIRECT
+#define RT_SHADOW_REFILL_MIN_DIRECT 40
+#endif
+template <int MIN_WAIT = RT_SHADOW_REFILL_MIN, bool DIRECT = false>
 __global__ void __launch_bounds__(WAVE, RT_SHADOW_REFILL_MIN_WAVES) k_trace_shadow_refill(const SceneView sc, const TraceParams tp, const ShadowSoA shadow,
                                                                                      const RayQueue queue, const float limit, const int img_w,
                                                                                      float4 *__restrict__ temp_buf, float4 *__restrict__ out_rc,
@@ -95,6 +100,18 @@ __global__ void __launch_bounds__(WAVE, RT_SHADOW_REFILL_MIN_WAVES) k_trace_shad
         h = make_hit();
         h.t = dist;
         size = 0;
+        if (DIRECT) { // ... + the entry of the one instance (what part C does at its leaf)
+            // (an instance shadow rays do not see, a BLAS whose root is the sentinel: the segment is through, nothing hit)
+            const bool walk_it = (sc.direct.ray_visibility & (1u << RAY_TYPE_SHADOW)) != 0 && sc.direct.root != BVH4_SENTINEL;
+            o = transform_point(ro, sc.direct.inv_xform);
+            d = transform_direction(rd, sc.direct.inv_xform);
+            inv_d = safe_invert(d);
+            st.write_at(size++, BVH4_SENTINEL);
+            tos = BVH4_SENTINEL;
+            cur = walk_it ? sc.direct.root : BVH4_SENTINEL;
+            lvl = walk_it ? BLAS : TLAS;
+            return;
+        }
         st.write_at(size++, BVH4_SENTINEL);
         tos = BVH4_SENTINEL;
         cur = tp.root_index;
@@ -107,7 +124,9 @@ __global__ void __launch_bounds__(WAVE, RT_SHADOW_REFILL_MIN_WAVES) k_trace_shad
     auto leave_blas = [&]() { // the pop that ends a BLAS walk hands back the sentinel and restores the top-level `tos`
         if (lvl == BLAS && cur == BVH4_SENTINEL) {
             lvl = TLAS;
-            pop();
+            if (!DIRECT) {
+                pop();
+            }
         }
     };
     auto deliver = [&](const f3 rc, const uint32_t xy_virtual) {
@@ -141,7 +160,7 @@ __global__ void __launch_bounds__(WAVE, RT_SHADOW_REFILL_MIN_WAVES) k_trace_shad
             } else if (at_leaf) {
                 const int tri_start = int(cur & BVH2_PRIM_INDEX_BITS), tri_end = int(tri_start + ((cur & BVH2_PRIM_COUNT_BITS) >> 29) + 1);
                 bool stop = false;
-                if (intersect_tris_any(o, d, tri_table(sc), sc.tri_materials, sc.tri_indices, tri_start, tri_end, int(mi_index), h)) {
+                if (intersect_tris_any(o, d, tri_table(sc), sc.tri_materials, sc.tri_indices, tri_start, tri_end, DIRECT ? int(sc.direct.mi) : int(mi_index), h)) {
                     // (blas leaf of traverse_any: the side that was hit)
                     const bool is_backfacing = h.prim_index < 0;
                     const uint32_t prim = is_backfacing ? uint32_t(-h.prim_index - 1) : uint32_t(h.prim_index);
@@ -252,6 +271,9 @@ __global__ void __launch_bounds__(WAVE, RT_SHADOW_REFILL_MIN_WAVES) k_trace_shad
         }
 
         // ---- service part, C: top-level steps until every lane is inside an instance or through with its segment
+        if (DIRECT) {
+            continue; // (no top level: begin_segment entered the instance)
+        }
         for (;;) {
             const bool in_c = (lvl == TLAS) && (cur != BVH4_SENTINEL);
             if (__builtin_amdgcn_readfirstlane(int(__ballot(in_c) == 0ull))) {

@@ -97,6 +97,10 @@ struct rayhip_ctx {
     bool refill_pool = false;           // RAYHIP_REFILL=4: 3 + the secondary bounces of 4-wide scenes through the pooled kernel (k_trace_closest_pool)
     int pool_waves = 0, pool_resident = 0; // its grid
     bool pool_scene = false;               // ... and whether the scene in place suits it (refresh_scene_view)
+    bool direct_entry = true;  // RAYHIP_DIRECT_ENTRY=0: one-instance scenes walk their top level like any other (kernels_closest_refill.hip.h: DIRECT)
+    bool direct_scene = false; // ... whether the scene in place has ONE instance over the 4-wide tree, SceneView::direct filled (refresh_top_level_view)
+    // the direct-entry form of the persistent walks replaces the generic one in every launch of them
+    bool direct() const { return wide == 4 && direct_entry && direct_scene && sc.direct.on != 0u; }
 
     DevBuf pmj, filter_table;
     // scene
@@ -714,6 +718,9 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
         // chunks whole (the plain kernel's schedule without its 60 spilled registers per ray: 2.13 vs 2.10 ms per iteration for
         // K2, 7.8 GB fewer scratch writes per primary launch)
         const int mode = getenv("RAYHIP_REFILL") != nullptr ? atoi(getenv("RAYHIP_REFILL")) : 3;
+        if (const char *e = getenv("RAYHIP_DIRECT_ENTRY")) {
+            c->direct_entry = atoi(e) != 0;
+        }
         if (mode != 0) {
             int per_cu_refill = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_refill, k_trace_closest_refill<8>, WAVE, 0) != hipSuccess || per_cu_refill <= 0) {

@@ -104,6 +104,8 @@ int rayhip_k_intersect_closest(rayhip_ctx *c, const rayhip_camera *cam, rayhip_r
             k_trace_closest_pool<><<<std::max(1, std::min(g, c->pool_waves)), WAVE, 0, s>>>(c->sc, tp, c->rays[0], c->hits, q, 0, c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h));
         } else if (c->wide == 8 && c->refill_waves) {
             k_trace_closest_refill<8><<<std::max(1, std::min(g, c->refill_waves)), WAVE, 0, s>>>(c->sc, tp, c->rays[0], c->hits, q, 0, c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
+        } else if (c->wide == 4 && c->refill_waves && c->direct()) {
+            k_trace_closest_refill<4, RT_REFILL_MIN_DIRECT, true><<<std::max(1, std::min(g, c->refill_waves)), WAVE, 0, s>>>(c->sc, tp, c->rays[0], c->hits, q, 0, c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
         } else if (c->wide == 4 && c->refill_waves) {
             k_trace_closest_refill<4><<<std::max(1, std::min(g, c->refill_waves)), WAVE, 0, s>>>(c->sc, tp, c->rays[0], c->hits, q, 0, c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
         } else if (c->wide == 8) {
@@ -174,7 +176,10 @@ int rayhip_k_intersect_shadow(rayhip_ctx *c, const rayhip_camera *cam, const ray
     const TraceParams tp = make_trace_params(*cam, c->sc.tlas_root, iteration);
     const int g = int(std::min<size_t>(size_t(c->grid_waves), (size_t(count) + WAVE - 1) / WAVE));
     // results land in the (otherwise idle) hit plane
-    if (getenv("RAYHIP_HOOK_SHADOW_REFILL") && c->wide == 4) { // the product's flat persistent form over the 4-wide tree (no counters)
+    if (getenv("RAYHIP_HOOK_SHADOW_REFILL") && c->wide == 4 && c->direct()) { // ... its direct-entry form, where the passes launch that
+        k_trace_shadow_refill<RT_SHADOW_REFILL_MIN_DIRECT, true><<<g ? g : 1, WAVE, 0, s>>>(c->sc, tp, c->shadow, c->shadow_queue(0, size_t(count), 1), FLT_MAX, c->w, c->px.temp,
+                                                                                         c->hit_planes[0].as<float4>(), c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
+    } else if (getenv("RAYHIP_HOOK_SHADOW_REFILL") && c->wide == 4) { // the product's flat persistent form over the 4-wide tree (no counters)
         k_trace_shadow_refill<<<g ? g : 1, WAVE, 0, s>>>(c->sc, tp, c->shadow, c->shadow_queue(0, size_t(count), 1), FLT_MAX, c->w, c->px.temp,
                                                        c->hit_planes[0].as<float4>(), c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
     } else {

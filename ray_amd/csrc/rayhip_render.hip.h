@@ -149,6 +149,8 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
             // (static walk: this launch takes a chunk every ~8 ns chip-wide, more than one counter can hand out -- wavefront.hip.h)
             if (wide == 8) {
                 k_trace_closest_refill<8, WAVE><<<gtrace, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, nullptr);
+            } else if (c->direct()) { // one instance: entered from the kernel arguments (kernels_closest_refill.hip.h: DIRECT)
+                k_trace_closest_refill<4, WAVE, true><<<gtrace, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, nullptr);
             } else {
                 k_trace_closest_refill<4, WAVE><<<gtrace, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, nullptr);
             }
@@ -169,6 +171,8 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
             const int grid = work ? dyn_grid(resident, expect) : static_grid(std::min(gtrace, want), resident, expect);
             if (wide == 8) {
                 k_trace_closest_refill<8><<<grid, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, work);
+            } else if (c->direct()) {
+                k_trace_closest_refill<4, RT_REFILL_MIN_DIRECT, true><<<grid, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, work);
             } else {
                 k_trace_closest_refill<4><<<grid, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, work);
             }
@@ -304,8 +308,15 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
             } else if (wide == 4 && c->shadow_refill) { // the flat persistent form (kernels_shadow.hip.h)
                 uint32_t *work = c->next_work();
                 const uint32_t expect = c->expect_chunks(bounce, 1, nslots, stripes);
-                k_trace_shadow_refill<<<work ? dyn_grid(c->shadow_resident, expect) : static_grid(gtrace, c->shadow_resident, expect), WAVE, 0, ss>>>(
-                    c->sc, tp, c->shadow, c->shadow_queue(bounce, nslots, stripes), limit, vw, c->px.temp, nullptr, side ? c->stack_spill2.as<uint32_t>() : spill, layers, work);
+                const int grid = work ? dyn_grid(c->shadow_resident, expect) : static_grid(gtrace, c->shadow_resident, expect);
+                uint32_t *k3_spill = side ? c->stack_spill2.as<uint32_t>() : spill;
+                if (c->direct()) { // one instance: entered from the kernel arguments (kernels_shadow.hip.h: DIRECT)
+                    k_trace_shadow_refill<RT_SHADOW_REFILL_MIN_DIRECT, true><<<grid, WAVE, 0, ss>>>(c->sc, tp, c->shadow, c->shadow_queue(bounce, nslots, stripes), limit, vw,
+                                                                                                  c->px.temp, nullptr, k3_spill, layers, work);
+                } else {
+                    k_trace_shadow_refill<<<grid, WAVE, 0, ss>>>(c->sc, tp, c->shadow, c->shadow_queue(bounce, nslots, stripes), limit, vw, c->px.temp, nullptr, k3_spill,
+                                                                 layers, work);
+                }
             } else if (wide == 8 && (c->small_scene || c->tune_shadow_waves == 5)) {
                 k_trace_shadow<false, 8, RT_TRACE_SMALL_WAVES><<<gtrace, WAVE, 0, s>>>(K3_ARGS);
             } else if (wide == 8) {

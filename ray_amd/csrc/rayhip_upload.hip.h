@@ -172,6 +172,23 @@ static void refresh_top_level_view(rayhip_ctx *c, const uint32_t tlas_root, cons
     // level, which is every ray of a scene with ONE instance (RAYHIP_POOL_ANY=1: the pooled kernel for any scene -- tests of its other path)
     c->pool_scene = (live_instances == 1 || getenv("RAYHIP_POOL_ANY") != nullptr) && c->instances_count < (1u << 24);
     c->sc.tlas_root = tlas_root;
+    // the direct-entry form of the persistent walks (kernels_closest_refill.hip.h: DIRECT) takes the one instance from the kernel arguments:
+    // its record and the root of its 4-wide tree, from the host's copies of what the device holds (rayhip_ctx::refit: the live slots and
+    // the instance array of the last upload / instance update; mesh_refs: the roots, which a vertex update keeps current)
+    c->direct_scene = false;
+    c->sc.direct = DirectInstance{};
+    if (live_instances == 1 && tlas_root != 0xffffffffu && c->wide == 4 && c->refit.live.size() == 1 && c->refit.live[0] < c->refit.instances.size() &&
+        c->refit.live[0] < c->instances_count) {
+        const uint32_t mi = c->refit.live[0];
+        const rayhip_mesh_instance &inst = c->refit.instances[mi];
+        const auto ref = c->mesh_refs.find(inst.mesh_index);
+        if (ref != c->mesh_refs.end() && ref->second.node_index == inst.node_index) {
+            memcpy(c->sc.direct.inv_xform, inst.inv_xform, sizeof(inst.inv_xform));
+            c->sc.direct.ray_visibility = inst.ray_visibility;
+            c->sc.direct.mi = mi, c->sc.direct.root = ref->second.root4, c->sc.direct.on = 1u;
+            c->direct_scene = true;
+        }
+    }
     // ray-sort grid: true bounds of the TLAS root (Scene::GetBounds takes fminf for the max corner, SceneCPU.cpp:1553)
     for (int i = 0; i < 3; ++i) {
         const bool have = root_box.lo[i] <= root_box.hi[i];
@@ -615,6 +632,8 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
     return 0;
 }
 
+int rayhip_direct_entry(rayhip_ctx *c) { return c && c->have_scene && c->direct() && (c->refill_waves || c->shadow_refill) ? 1 : 0; }
+
 int rayhip_scene_bvh_width(rayhip_ctx *c) { return !c || !c->have_scene ? 0 : c->wide ? c->wide : 2; }
 
 int rayhip_closest_hit_form(rayhip_ctx *c) {
@@ -711,8 +730,8 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
     if (upload_sky(c, d)) {
         return 1;
     }
+    c->refit.live = live, c->refit.instances = mis; // (what a later rayhip_scene_update_vertices rebuilds the top level over, and the direct entry's source)
     refresh_scene_view(c, d, tlas_root, root_box, uint32_t(live.size()));
-    c->refit.live = live, c->refit.instances = mis; // (what a later rayhip_scene_update_vertices rebuilds the top level over)
     trace("instances updated");
     return 0;
 }

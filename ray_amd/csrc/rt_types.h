@@ -28,6 +28,17 @@ struct SkyView {
     const uint8_t *weather, *noise3d, *curl, *moon, *cirrus;
 };
 
+// The ONE instance of a scene whose top level holds a single instance, as the direct-entry form of the persistent walks takes it
+// (kernels_closest_refill.hip.h): it travels in the kernel arguments, so every read of it is a scalar load of a uniform value.
+// Filled by refresh_top_level_view (rayhip_upload.hip.h) from the arrays the device holds; on == 0: more than one instance, or none.
+struct DirectInstance {
+    float inv_xform[16];     // rayhip_mesh_instance::inv_xform of that instance
+    uint32_t ray_visibility; // ... its ray_visibility word
+    uint32_t mi;             // its slot in mesh_instances (the obj_index of its hits)
+    uint32_t root;           // blas_root4[mi]
+    uint32_t on;
+};
+
 // Device-side view of the flat scene (pointers into HBM).  Mirrors reference Core.h:511-535 scene_data_t.
 struct SceneView {
     const rayhip_bvh2_node *nodes;
@@ -64,6 +75,7 @@ struct SceneView {
     uint32_t tlas_root;
     rayhip_environment env;
     SkyView sky;
+    DirectInstance direct; // (last: the offsets of everything above are what they were)
 };
 
 // ---- light_t bitfield accessors (Core.h:197-205; GCC packs bitfields LSB first) --------------------

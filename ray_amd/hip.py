@@ -102,7 +102,7 @@ assert LIGHT_NODE_DTYPE.itemsize == 208
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "scene_refit_lights", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "scene_refit_lights", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
@@ -150,6 +150,7 @@ class Library:
         f("scene_bvh_width").argtypes = [vp]
         if prefix == "rayhip_":
             f("closest_hit_form").argtypes = [vp]
+            f("direct_entry").argtypes = [vp]
         f("reserve_batch").argtypes = [vp, C.c_int]
         f("set_tonemap_lut").argtypes = [vp, C.c_int, vp, C.c_int]
         f("denoise_nlm").argtypes = [vp, C.POINTER(Camera), C.POINTER(C.c_int * 4), C.c_int]
@@ -416,6 +417,10 @@ class Context:
     def closest_hit_form(self) -> int:
         """0: one ray per lane; 1: persistent refill kernel; 2: the pooled kernel (include/rayhip.h)"""
         return int(self.L.fn("closest_hit_form")(self._ctx)) if self.L.prefix == "rayhip_" else 0
+
+    def direct_entry(self) -> int:
+        """1: the persistent walks enter the scene's one instance from their arguments; 0: they walk the top level (include/rayhip.h)"""
+        return int(self.L.fn("direct_entry")(self._ctx)) if self.L.prefix == "rayhip_" else 0
 
     def max_batch(self) -> int:
         """largest number of iterations one wavefront pass of the current frame can carry"""

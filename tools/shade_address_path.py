@@ -57,7 +57,7 @@ def frame_chunks(bench_log):
     shadow = d["roofline"]["shadow_kernel"]["rays_per_sample"]
     return {"shade::k_surface_scatter<true": primary, "shade::k_surface_scatter<false": (rps - 1.0) * primary,
             "shade::k_light_pick_first": rps * primary, "shade::k_scatter<true, false": shadow * primary,
-            "k_trace_closest_refill<4, 64>": primary, "k_trace_closest_refill<4, 40>": (rps - 1.0) * primary}
+            "k_trace_closest_refill<4, 64": primary, "k_trace_closest_refill<4, 40": (rps - 1.0) * primary}
 
 
 def full_frames(rows):

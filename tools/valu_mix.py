@@ -99,7 +99,7 @@ def main():
         subprocess.run([g._hipcc(), *[f for f in g.RAYHIP_FLAGS if f not in ("-fPIC",)], "--cuda-device-only", "-S", "rayhip.hip", "-o", s_path], cwd=csrc, check=True,
                        stderr=subprocess.DEVNULL)
         asm = open(s_path).read()
-    mix, ops, n_blocks = kernel_loop_mix(asm, "_ZN2rt22k_trace_closest_refillILi4ELi40EEE")
+    mix, ops, n_blocks = kernel_loop_mix(asm, "_ZN2rt22k_trace_closest_refillILi4ELi40ELb0EEE")
     n = sum(mix.values())
     serial = sum(mix[c] * COST[c] for c in mix)
     paired = max(mix["half"] * COST["half"] + mix["quarter"] * COST["quarter"], 2.15 * n)
