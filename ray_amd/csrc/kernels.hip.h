@@ -13,7 +13,8 @@
 //                                               fixed grid and grid-strides over the count it reads there, so the
 //                                               bounce loop never returns to the host (RendererVK.cpp:641-712 records
 //                                               all bounces up front for the same reason)
-//   K10 mix_incremental + K11 postprocess    -> k_accumulate (fused: one pass over the rect)
+//   K10 mix_incremental + K11 postprocess    -> k_accumulate (fused: one pass over the rect), k_accumulate_interleaved (layered passes
+//                                               whose layers are interleaved: Layering, rt_base.h)
 //
 // Conventions
 //   * one wavefront (64 lanes) per workgroup in the traversal kernels: the traversal stack is a per-wavefront
@@ -233,7 +234,9 @@ __global__ void __launch_bounds__(256) k_raygen(const RayGenParams p, const uint
                 pl.iteration = p.iteration + int(layer);
                 pl.rand_seed = layer_rand_seed(pl.iteration);
                 generate_primary_ray(pl, pmj, filter_table, x, y, r, h);
-                r.xy += layer_offset_xy(layers, layer);
+            }
+            if (layers.count > 1) { // (interleaved layers move layer 0 too)
+                r.xy = layer_xy(layers, r.xy, layer);
             }
             store_ray(rays, slot, r, p.skip_ior == 0);
             store_hit(hits, slot, h);
@@ -438,8 +441,27 @@ __global__ void __launch_bounds__(256) k_reorder_rays(const RaySoA src, const Ra
 }
 
 // ---- K10 + K11 ----------------------------------------------------------------------------------------------
+// One layer of a batched pass folded into a pixel's state: the aux blends (blend_aux_pixel, rt_pixel.h, on the register copies), then the
+// accumulate step.  `temp`, `aux_base`, `aux_dn`: this pixel's elements on that layer -- in memory (k_accumulate) or staged in LDS
+// (k_accumulate_interleaved).  Written once, so that both kernels fold with the same operations in the same order: the same bits.
+__device__ __forceinline__ void fold_layer(AccumParams &pl, const AccumLayer &al, const float4 *temp, const float4 *aux_base, const float4 *aux_dn,
+                                           AccumPixel &st, f4 &base, f4 &dn) {
+    pl.iteration = al.iteration;
+    pl.mix_factor = al.mix_factor, pl.half_mix_factor = al.half_mix_factor;
+    pl.is_class_a = al.is_class_a, pl.variance_threshold = al.variance_threshold;
+    // (a one-by-one run samples the pixel in this iteration iff the previous accumulate left it queued)
+    if (!(st.required < pl.iteration)) {
+        const float4 nb = *aux_base, nd = *aux_dn;
+        base += (f4{nb.x, nb.y, nb.z, nb.w} - base) * pl.mix_factor;
+        dn += (f4{nd.x, nd.y, nd.z, nd.w} - dn) * pl.mix_factor;
+    }
+    accumulate_step(pl, *temp, st);
+}
+
 // Batched passes: `per_layer` describes layers [layer_base, layer_base + layer_count) (kernel arguments hold at most
 // MAX_BATCH of them; longer passes fold their layers in several launches, in order).
+// One thread per pixel: plain passes, and layered ones whose layers lie side by side (Layering::interleaved == 0), where neighbouring
+// lanes read neighbouring elements of a layer.
 __global__ void __launch_bounds__(256) k_accumulate(const AccumParams p, const PixelBuffers px, const Layering layers,
                                                    const AccumLayers per_layer, const int layer_base, const int layer_count) {
     const int n = p.rect[2] * p.rect[3];
@@ -462,23 +484,91 @@ __global__ void __launch_bounds__(256) k_accumulate(const AccumParams p, const P
         f4 base = {b0.x, b0.y, b0.z, b0.w}, dn = {d0.x, d0.y, d0.z, d0.w};
         AccumParams pl = p;
         for (int k = 0; k < layer_count; ++k) {
-            pl.iteration = per_layer.l[k].iteration;
-            pl.mix_factor = per_layer.l[k].mix_factor, pl.half_mix_factor = per_layer.l[k].half_mix_factor;
-            pl.is_class_a = per_layer.l[k].is_class_a, pl.variance_threshold = per_layer.l[k].variance_threshold;
             // this pixel on layer layer_base + k of the virtual frame
             const uint32_t off = layer_offset_xy(layers, uint32_t(layer_base + k));
             const size_t vidx = (size_t(off & 0xffffu) + size_t(y)) * pitch + size_t(off >> 16) + size_t(x);
-            // (a one-by-one run samples the pixel in this iteration iff the previous accumulate left it queued)
-            if (!(st.required < pl.iteration)) { // blend_aux_pixel (rt_pixel.h) on the register copies
-                const float4 nb = px.aux_base_layers[vidx], nd = px.aux_dn_layers[vidx];
-                base += (f4{nb.x, nb.y, nb.z, nb.w} - base) * pl.mix_factor;
-                dn += (f4{nd.x, nd.y, nd.z, nd.w} - dn) * pl.mix_factor;
-            }
-            accumulate_step(pl, px.temp[vidx], st);
+            fold_layer(pl, per_layer.l[k], px.temp + vidx, px.aux_base_layers + vidx, px.aux_dn_layers + vidx, st, base, dn);
         }
         px.base_color[idx] = mkfloat4(base.x, base.y, base.z, base.w);
         px.depth_normals[idx] = mkfloat4(dn.x, dn.y, dn.z, dn.w);
         store_accum_pixel(pl, idx, st, px.variance + idx, px.full, px.half, px.raw, px.final_, px.required_samples);
+    }
+}
+
+// The same fold over interleaved layers (Layering::interleaved == 1, count > 1).  A pixel's layers are adjacent there, so a thread per
+// pixel would read with a stride of cols * 16 bytes between lanes.  Instead a block takes a strip of ACCUM_STRIP pixels of a frame row and
+// walks its layers in segments of up to `seg_cols` neighbouring slots of one virtual row: all 256 threads copy the segment -- per pixel a
+// run of seg_cols * 16 bytes of each per-iteration buffer, one whole 128-byte line when cols is a multiple of 8 (make_layering) -- to LDS,
+// then thread j < ACCUM_STRIP folds pixel j of the strip from LDS, layer after layer, its state in registers as above.
+// Dynamic LDS: 3 * (ACCUM_STRIP * seg_cols + 1) float4 (48 KiB: three blocks, six folding wavefronts per CU).
+constexpr int ACCUM_STRIP = 128;
+constexpr int ACCUM_SEG_COLS = 8;
+constexpr int ACCUM_LOADS = ACCUM_STRIP * ACCUM_SEG_COLS / 256; // elements of a segment per thread and buffer (the block is 256 threads)
+static_assert(ACCUM_LOADS * 256 == ACCUM_STRIP * ACCUM_SEG_COLS, "a segment is a whole number of rounds of the block");
+__global__ void __launch_bounds__(256) k_accumulate_interleaved(const AccumParams p, const PixelBuffers px, const Layering layers,
+                                                               const AccumLayers per_layer, const int layer_base, const int layer_count,
+                                                               const int seg_cols) {
+    extern __shared__ float4 accum_lds[];
+    const int stage = ACCUM_STRIP * seg_cols + 1; // elements of a buffer's stage: the strip's pixels x seg_cols layer slots + one spare
+    float4 *const s_temp = accum_lds, *const s_base = accum_lds + stage, *const s_dn = accum_lds + 2 * stage;
+    const size_t pitch = size_t(virtual_width(layers));
+    const int cols = layers.cols, rows = layers.rows;
+    const int strips_x = (p.rect[2] + ACCUM_STRIP - 1) / ACCUM_STRIP, n_strips = strips_x * p.rect[3];
+    const int tid = int(threadIdx.x);
+    for (int strip = blockIdx.x; strip < n_strips; strip += gridDim.x) {
+        const int y = p.rect[1] + strip / strips_x, x0 = p.rect[0] + (strip % strips_x) * ACCUM_STRIP;
+        const int np = min(ACCUM_STRIP, p.rect[0] + p.rect[2] - x0); // pixels of this strip
+        const int x = x0 + tid;
+        const bool mine = tid < np && pixel_owned(p.shard, p.w, x, y);
+        if (!__syncthreads_or(mine ? 1 : 0)) { // (also orders this strip's staging behind the previous strip's fold)
+            continue; // another rank's pixels: stay zero here, filled in by the frame reduce
+        }
+        const int idx = y * p.w + (mine ? x : x0);
+        AccumPixel st = {};
+        f4 base = {}, dn = {};
+        if (mine) {
+            st = load_accum_pixel(idx, px.full, px.half, px.required_samples);
+            const float4 b0 = px.base_color[idx], d0 = px.depth_normals[idx];
+            base = {b0.x, b0.y, b0.z, b0.w}, dn = {d0.x, d0.y, d0.z, d0.w};
+        }
+        AccumParams pl = p;
+        // the layers of this launch, in order, in segments that stay inside one virtual row and one LDS stage
+        for (int l0 = layer_base, end = layer_base + layer_count; l0 < end;) {
+            const int vr = l0 / cols, c0 = l0 - vr * cols;
+            const int len = min(min(seg_cols, cols - c0), end - l0);
+            // element e of the stage: pixel e / len of the strip, layer slot c0 + e % len
+            const size_t row0 = (size_t(y) * size_t(rows) + size_t(vr)) * pitch + size_t(x0) * size_t(cols) + size_t(c0);
+            const uint32_t rcp = layer_rcp(uint32_t(len));
+            // (a full segment's rows are 128 bytes: slot c of pixel j sits at c ^ (j & 7), so that the fold's reads of one slot by neighbouring
+            // lanes spread over the banks instead of meeting in two of them)
+            const int swizzle = len == 8 ? 7 : 0;
+            const int n_elems = np * len; // <= ACCUM_STRIP * ACCUM_SEG_COLS = ACCUM_LOADS * 256: one round of the block
+            // (no branch in the round -- a thread past the end reads the last element again and writes the spare slot behind its stage --
+            // so that every load of the round is in flight before the first store waits)
+#pragma unroll
+            for (int u = 0; u < ACCUM_LOADS; ++u) {
+                const int e = tid + u * 256, e_in = min(e, n_elems - 1);
+                const int j = int(div_by_rcp(uint32_t(e_in), rcp));
+                const size_t g = row0 + size_t(j) * size_t(cols) + size_t(e_in - j * len);
+                const float4 t = px.temp[g], b = px.aux_base_layers[g], d = px.aux_dn_layers[g];
+                const int e_out = e < n_elems ? j * len + ((e_in - j * len) ^ (j & swizzle)) : stage - 1;
+                s_temp[e_out] = t, s_base[e_out] = b, s_dn[e_out] = d;
+            }
+            __syncthreads();
+            if (mine) {
+                for (int k = 0; k < len; ++k) {
+                    const int e = tid * len + (k ^ (tid & swizzle));
+                    fold_layer(pl, per_layer.l[l0 - layer_base + k], s_temp + e, s_base + e, s_dn + e, st, base, dn);
+                }
+            }
+            __syncthreads();
+            l0 += len;
+        }
+        if (mine) {
+            px.base_color[idx] = mkfloat4(base.x, base.y, base.z, base.w);
+            px.depth_normals[idx] = mkfloat4(dn.x, dn.y, dn.z, dn.w);
+            store_accum_pixel(pl, idx, st, px.variance + idx, px.full, px.half, px.raw, px.final_, px.required_samples);
+        }
     }
 }
 

@@ -255,8 +255,8 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
                     if (layer != 0) { // a later iteration of the batch: its own sample index / seed, keyed by the real pixel
                         tpl.iteration = tp.iteration + int(layer);
                         tpl.rand_seed = layer_rand_seed(tpl.iteration);
-                        r.xy = xy_real(xy_virtual, layers, layer);
                     }
+                    r.xy = xy_real(xy_virtual, layers, layer); // (interleaved layers: layer 0 is not the real pixel either)
                     const uint32_t rand_hash = hash_combine(hash(r.xy), tpl.rand_seed);
                     uint32_t rand_dim = RAND_DIM_BASE_COUNT + get_total_depth(r.depth) * RAND_DIM_BOUNCE_COUNT;
                     const uint32_t depth_in = r.depth;

@@ -86,11 +86,15 @@ struct rayhip_ctx {
     // RAYHIP_PRIMARY_WAVES / RAYHIP_SHADOW_WAVES: register footprint of the plain K2 (primary rays) / of K3.  K3 runs at 5 waves per
     // SIMD (96 VGPRs, 32 spilled registers per ray instead of 51 at 6 waves: same time, a third less scratch traffic)
     int tune_primary_waves = 0, tune_shadow_waves = 5;
-    // layered passes: a primary wavefront holds S samples of each of 64 / S pixels of an 8x8 tile (RayGenTiling).  Measured on the headline
-    // scene, 64-layer passes (profiles/r04/experiments/raygen_samples_per_wave.txt): primary K2 268 / 250 / 237 / 223 us per sample for
-    // S = 1 / 4 / 16 / 64 -- the S rays of a pixel walk the same nodes -- and the primary shade 287 / 294 / 397 / 545: its three 16-byte
-    // pixel writes per ray stay in runs of four pixels at S = 4 and scatter over the layers beyond.  4 is the default; RAYHIP_RAYGEN_SAMPLES
-    int raygen_samples_per_wave = 4;
+    // layered passes: a primary wavefront holds S samples of each of 64 / S pixels of an 8x8 tile (RayGenTiling); the S rays of a pixel walk the
+    // same nodes, hit the same triangle and read the same material.  Measured on the headline scene, ms per 64-spp frame, S = 4 / 16 / 64
+    // (profiles/layer_layout/README.md): primary K2 13.9 / 13.1 / 12.6 whatever the layout; the primary shade 12.4 / 16.0 / 23.0 while whole
+    // layers lay side by side -- its three 16-byte pixel writes per ray scattered over the layers -- and 12.4 / 12.1 / 12.0 with a pixel's layers
+    // adjacent (layer_layout below), where the secondary shade follows: 47.8 / 46.9 / 46.5.  64 is the default; RAYHIP_RAYGEN_SAMPLES
+    int raygen_samples_per_wave = 64;
+    // how the layers of a pass lie in the per-iteration pixel buffers (Layering, rt_base.h): 1 = a pixel's layers adjacent, 0 = whole
+    // layers side by side.  RAYHIP_LAYER_LAYOUT
+    int layer_layout = 1;
     bool shadow_refill = true; // K3 as the flat persistent kernel (4-wide walk); RAYHIP_SHADOW_REFILL=0: the nested form
     bool refill_secondary_only = false; // RAYHIP_REFILL=2: primary rays (coherent, every lane busy to the end) keep the plain kernel
     bool refill_primary_whole = false;  // RAYHIP_REFILL=3: ... or take the flat kernel with whole-chunk refills (no spill stores in the walk)
@@ -394,27 +398,7 @@ int use_device(rayhip_ctx *c) {
 // wavefront-state slots a w x h rect needs: ray generation deals whole 8x8 pixel tiles (k_raygen)
 size_t tile_slots(int w, int h) { return size_t((w + 7) / 8) * size_t((h + 7) / 8) * 64u; }
 
-// Most iterations one pass can carry (Layering, rt_base.h): layers are stacked `cols` wide and `rows` high in a virtual
-// frame whose coordinates must fit the two 16-bit halves of ray_data_t::xy.
-constexpr int MAX_LAYERS = 512;
-int max_layers_for(int w, int h) {
-    if (w <= 0 || h <= 0) {
-        return 0;
-    }
-    // (the pixel helpers index the virtual frame with 32-bit ints: cols * rows * w * h must stay below 2^31; make_layering
-    // rounds the layer count up to whole columns, hence the margin of one column)
-    const size_t npix = size_t(w) * size_t(h), max_rows = size_t(65535 / h);
-    const size_t by_index = ((size_t(1) << 31) - 1) / npix;
-    const size_t by_index_cols = by_index > max_rows ? (by_index / max_rows) * max_rows : by_index;
-    return int(std::max<size_t>(1, std::min<size_t>({size_t(MAX_LAYERS), size_t(65535 / w) * max_rows, by_index_cols})));
-}
-// the virtual frame of a pass of `layers` iterations: as few columns as the row limit allows
-Layering make_layering(int w, int h, int layers) {
-    const int max_rows = std::max(1, 65535 / h);
-    const int cols = (layers + max_rows - 1) / max_rows;
-    return Layering{h, layers, w, std::max(1, cols)};
-}
-int layer_rows(const Layering &L) { return (L.count + L.cols - 1) / L.cols; }
+// (the virtual frame of a layered pass -- max_layers_for, make_layering, layer_rows: rt_base.h, shared with the host build)
 // slots a pass of `layers` iterations over a rect needs under the context's shard (k_raygen's tiling)
 size_t pass_slots(const rayhip_ctx *c, int frame_w, int frame_h, int rect_w, int rect_h, int layers) {
     return size_t(make_raygen_tiling(frame_w, frame_h, rect_w, rect_h, c->shard).tiles) * 64u * size_t(layers);
@@ -422,7 +406,7 @@ size_t pass_slots(const rayhip_ctx *c, int frame_w, int frame_h, int rect_w, int
 
 int alloc_frame(rayhip_ctx *c, int w, int h, int layers) {
     const size_t npix = size_t(w) * size_t(h);
-    const Layering L = make_layering(w, h, layers);
+    const Layering L = make_layering(w, h, layers, c->layer_layout);
     const size_t vpix = npix * size_t(L.cols) * size_t(layer_rows(L)); // the virtual frame (>= npix * layers)
     if (c->px_temp.alloc(vpix * 16) ||
         (layers > 1 && (c->px_aux_base.alloc(vpix * 16) || c->px_aux_dn.alloc(vpix * 16))) || c->px_full.alloc(npix * 16) || c->px_half.alloc(npix * 16) || c->px_raw.alloc(npix * 16) ||
@@ -677,6 +661,9 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
     if (const char *e = getenv("RAYHIP_RAYGEN_SAMPLES")) {
         const int v = atoi(e);
         c->raygen_samples_per_wave = (v == 4 || v == 16 || v == 64) ? v : 1;
+    }
+    if (const char *e = getenv("RAYHIP_LAYER_LAYOUT")) {
+        c->layer_layout = atoi(e) != 0 ? 1 : 0;
     }
     if (const char *e = getenv("RAYHIP_SHADOW_REFILL")) {
         c->shadow_refill = atoi(e) != 0;

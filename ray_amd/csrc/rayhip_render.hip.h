@@ -4,7 +4,7 @@
 
 // do the allocated per-iteration pixel buffers and wavefront state hold a pass of `n` iterations over `rect`?
 static bool pass_fits(const rayhip_ctx *c, const int rect[4], int n) {
-    const Layering L = make_layering(c->w, c->h, n);
+    const Layering L = make_layering(c->w, c->h, n, c->layer_layout);
     const size_t vbytes = size_t(c->w) * size_t(c->h) * size_t(L.cols) * size_t(layer_rows(L)) * 16u;
     return vbytes <= c->px_temp.bytes && (n <= 1 || (vbytes <= c->px_aux_base.bytes && vbytes <= c->px_aux_dn.bytes)) &&
            pass_slots(c, c->w, c->h, rect[2], rect[3], n) + size_t(WAVE) * QUEUE_MAX_STRIPES <= c->slots_cap;
@@ -92,7 +92,7 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
     }
     hipStream_t s = c->stream;
     const size_t npix = size_t(rect[2]) * size_t(rect[3]);
-    const Layering layers = make_layering(c->w, c->h, count_iterations);
+    const Layering layers = make_layering(c->w, c->h, count_iterations, c->layer_layout);
     const int vw = virtual_width(layers); // row pitch of the per-iteration pixel buffers
     // ray slots: the 8x8 tiles the ray generator walks (this rank's share under a shard), one set per iteration in flight
     RayGenTiling tiling = make_raygen_tiling(c->w, c->h, rect[2], rect[3], c->shard);
@@ -361,7 +361,15 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
             const AccumParams al = make_accum_params(*cam, c->w, rect, iteration + base + k, c->shard);
             per_layer.l[k] = AccumLayer{al.iteration, al.mix_factor, al.half_mix_factor, al.is_class_a, al.variance_threshold};
         }
-        k_accumulate<<<grid_for(c, npix, 256), 256, 0, s>>>(ap, c->px, layers, per_layer, base, n);
+        if (layers.interleaved && layers.count > 1) {
+            // a block per strip of ACCUM_STRIP pixels of a row; it stages ACCUM_SEG_COLS layer slots of a virtual row at a time
+            const int seg_cols = std::min(layers.cols, ACCUM_SEG_COLS);
+            const size_t strips = size_t((rect[2] + ACCUM_STRIP - 1) / ACCUM_STRIP) * size_t(rect[3]);
+            const size_t lds = 3u * (size_t(ACCUM_STRIP) * size_t(seg_cols) + 1u) * sizeof(float4);
+            k_accumulate_interleaved<<<grid_for(c, strips * 256u, 256), 256, lds, s>>>(ap, c->px, layers, per_layer, base, n, seg_cols);
+        } else {
+            k_accumulate<<<grid_for(c, npix, 256), 256, 0, s>>>(ap, c->px, layers, per_layer, base, n);
+        }
     }
     if (c->census_on && !count && !count_wide) { // what the queues of this pass held: the next pass sizes its launches from it
         const int queues = (max_depth + 1) * rayhip_ctx::QUEUES_PER_BOUNCE;
@@ -392,7 +400,7 @@ int rayhip_max_batch(rayhip_ctx *c) {
     if (!c || !c->h) {
         return 0;
     }
-    return max_layers_for(c->w, c->h);
+    return max_layers_for(c->w, c->h, c->layer_layout);
 }
 
 int rayhip_reserve_batch(rayhip_ctx *c, int count) {

@@ -324,24 +324,121 @@ RT_HD f3 tangent_from_world(f3 T, f3 B, f3 N, f3 V) { return f3{dot(V, T), dot(V
 // running means in iteration order -- so a batch is bit-identical to the same iterations rendered one by one, but a
 // launch carries layers x more rays: small frames (a GPU's share of a tile-sharded frame, 256x256 previews) fill the
 // machine and the fixed cost of a launch (tail of its longest rays) is paid once per batch.
+//
+// Two forms of the virtual frame (Layering::interleaved, chosen per context: RAYHIP_LAYER_LAYOUT):
+//   0, side by side: whole layers next to each other, as above.  The 64 layers of a pixel lie 64 frames apart.
+//   1, interleaved:  the layers of a PIXEL next to each other.  The virtual frame is the real one with every pixel blown up to a block of
+//      `cols` x `rows` layer slots: xy = ((x * cols + l % cols) << 16) | (y * rows + l / cols), cols = min(count, 65535 / frame_w), rounded
+//      down to a multiple of 8 where the pass still fits (make_layering): 32 x 2 for 64 layers at 1080p, 512-byte runs on 128-byte lines.  A
+//      wavefront that holds many samples of one pixel (RayGenTiling::samples_per_wave) then writes runs of `cols` neighbouring
+//      16-byte elements instead of one element in each of 64 frames, and k_accumulate_interleaved reads a strip of pixels with all the
+//      layers of a virtual row as one contiguous span.
+// Everything that addresses a per-iteration buffer does so with y * pitch + x on the virtual xy (rt_pixel.h), whatever the form.  Going
+// back from a virtual xy to (layer, real xy) is one division of each half -- by (frame_w, frame_h) side by side, by (cols, rows)
+// interleaved -- done as a multiply-high by a reciprocal the host precomputes (exact for 16-bit operands: layer_rcp).
 struct Layering {
     int frame_h; // height of the real frame
     int count;   // layers in this pass (1 = plain single-iteration pass)
     int frame_w; // width of the real frame
     int cols;    // layers side by side in the virtual frame (>= 1)
+    // (a Layering written as {h, 1, w, 1} leaves the following zero: a single layer never looks at them)
+    int rows;        // rows of layers in the virtual frame: ceil(count / cols)
+    int interleaved; // 1: the layers of a pixel are adjacent; 0: whole layers side by side
+    uint32_t rcp_x, rcp_y; // layer_rcp of what the x / y half of a virtual xy is divided by
 };
 RT_HD Layering single_layer(const int w, const int h) { return Layering{h, 1, w, 1}; }
-// offset of layer `layer` inside the virtual frame, in the packed form of ray_data_t::xy
+// n / d for n < 2^16 and 1 <= d < 2^16 as a multiply-high: rcp = ceil(2^32 / d) overshoots 2^32 / d by e / d with e = rcp * d - 2^32 < d,
+// which moves n * rcp / 2^32 by n * e / (d * 2^32) < 1 / d: not past the next integer.  d = 1 has no 32-bit reciprocal and is marked by 0.
+RT_HD uint32_t layer_rcp(const uint32_t d) { return d > 1u ? 0xffffffffu / d + 1u : 0u; }
+RT_HD uint32_t div_by_rcp(const uint32_t n, const uint32_t rcp) { return rcp ? uint32_t((uint64_t(n) * uint64_t(rcp)) >> 32) : n; }
+// offset of layer `layer` inside the side-by-side virtual frame, in the packed form of ray_data_t::xy
 RT_HD uint32_t layer_offset_xy(const Layering L, const uint32_t layer) {
     const uint32_t lx = layer % uint32_t(L.cols), ly = layer / uint32_t(L.cols);
     return ((lx * uint32_t(L.frame_w)) << 16) + ly * uint32_t(L.frame_h);
 }
-RT_HD uint32_t xy_layer(const uint32_t xy, const Layering L) {
-    return L.count > 1 ? ((xy & 0xffffu) / uint32_t(L.frame_h)) * uint32_t(L.cols) + (xy >> 16) / uint32_t(L.frame_w) : 0u;
+// the virtual xy of real pixel `xy` (packed) on layer `layer` (ray generation; layer 0 of a plain pass is the pixel itself)
+RT_HD uint32_t layer_xy(const Layering L, const uint32_t xy, const uint32_t layer) {
+    if (!L.interleaved) {
+        return xy + layer_offset_xy(L, layer);
+    }
+    const uint32_t lx = layer % uint32_t(L.cols), ly = layer / uint32_t(L.cols);
+    return (((xy >> 16) * uint32_t(L.cols) + lx) << 16) | ((xy & 0xffffu) * uint32_t(L.rows) + ly);
 }
-RT_HD uint32_t xy_real(const uint32_t xy, const Layering L, const uint32_t layer) { return xy - layer_offset_xy(L, layer); }
+// a virtual xy taken apart: one division per half, the quotient and the remainder swap roles between the two forms
+RT_HD void xy_split(const uint32_t xy, const Layering L, uint32_t &layer, uint32_t &real) {
+    const uint32_t xv = xy >> 16, yv = xy & 0xffffu;
+    const uint32_t dx = uint32_t(L.interleaved ? L.cols : L.frame_w), dy = uint32_t(L.interleaved ? L.rows : L.frame_h);
+    const uint32_t qx = div_by_rcp(xv, L.rcp_x), qy = div_by_rcp(yv, L.rcp_y);
+    const uint32_t rx = xv - qx * dx, ry = yv - qy * dy;
+    const uint32_t lx = L.interleaved ? rx : qx, ly = L.interleaved ? ry : qy;
+    layer = ly * uint32_t(L.cols) + lx;
+    real = ((L.interleaved ? qx : rx) << 16) | (L.interleaved ? qy : ry);
+}
+RT_HD uint32_t xy_layer(const uint32_t xy, const Layering L) {
+    if (L.count <= 1) {
+        return 0u;
+    }
+    uint32_t layer, real;
+    xy_split(xy, L, layer, real);
+    return layer;
+}
+// (`layer` is xy_layer(xy, L): the callers hold it, and a plain pass needs no arithmetic at all)
+RT_HD uint32_t xy_real(const uint32_t xy, const Layering L, const uint32_t layer) {
+    if (L.count <= 1) {
+        return xy;
+    }
+    uint32_t l, real;
+    xy_split(xy, L, l, real);
+    (void)layer;
+    return real;
+}
 // width of the virtual frame = row pitch of the per-iteration buffers
 RT_HD int virtual_width(const Layering L) { return L.frame_w * L.cols; }
+
+// ---- the virtual frame of a pass, host side ---------------------------------------------------------------------------
+// Most iterations one pass can carry: the coordinates of the virtual frame must fit the two 16-bit halves of ray_data_t::xy -- that is
+// (65535 / w) * (65535 / h) layers in either form -- and the pixel helpers index it with 32-bit ints: cols * rows * w * h must stay below
+// 2^31.  make_layering rounds the layer count up to whole columns (side by side) / whole rows of `cols` slots (interleaved), hence the
+// rounding of the index bound to a multiple of the row / column limit.
+constexpr int MAX_LAYERS = 512;
+inline int max_layers_for(const int w, const int h, const int layout) {
+    if (w <= 0 || h <= 0) {
+        return 0;
+    }
+    const uint64_t npix = uint64_t(w) * uint64_t(h), max_rows = uint64_t(65535 / h), max_cols = uint64_t(65535 / w);
+    const uint64_t by_index = ((uint64_t(1) << 31) - 1) / npix;
+    const uint64_t unit = layout ? max_cols : max_rows; // slots that fill up before a second column / row is opened
+    const uint64_t by_index_whole = by_index > unit ? (by_index / unit) * unit : by_index;
+    uint64_t n = uint64_t(MAX_LAYERS);
+    n = max_cols * max_rows < n ? max_cols * max_rows : n;
+    n = by_index_whole < n ? by_index_whole : n;
+    return int(n < 1 ? 1 : n);
+}
+// the virtual frame of a pass of `layers` iterations.  layout 0: side by side, as few columns as the row limit allows; layout 1:
+// interleaved, as many columns as the 16-bit limit allows (a pixel's layers in as few runs as possible), in whole 128-byte lines
+inline Layering make_layering(const int w, const int h, const int layers, const int layout) {
+    Layering L = {h, layers, w, 1, 1, 0, 0u, 0u};
+    if (layers <= 1) {
+        return L;
+    }
+    if (layout) {
+        const int max_cols = 65535 / w > 1 ? 65535 / w : 1, max_rows = 65535 / h > 1 ? 65535 / h : 1;
+        L.cols = layers < max_cols ? layers : max_cols;
+        // a multiple of 8 where the pass still fits: a pixel's run of a virtual row then starts on a 128-byte line and is whole lines
+        const int cols8 = L.cols & ~7, rows8 = cols8 ? (layers + cols8 - 1) / cols8 : 0;
+        if (cols8 && rows8 <= max_rows && uint64_t(cols8) * uint64_t(rows8) * uint64_t(w) * uint64_t(h) < (uint64_t(1) << 31)) {
+            L.cols = cols8;
+        }
+        L.interleaved = 1;
+    } else {
+        const int max_rows = 65535 / h > 1 ? 65535 / h : 1;
+        L.cols = (layers + max_rows - 1) / max_rows;
+    }
+    L.rows = (layers + L.cols - 1) / L.cols;
+    L.rcp_x = layer_rcp(uint32_t(L.interleaved ? L.cols : w)), L.rcp_y = layer_rcp(uint32_t(L.interleaved ? L.rows : h));
+    return L;
+}
+inline int layer_rows(const Layering &L) { return (L.count + L.cols - 1) / L.cols; }
 
 struct Shard {
     int tile, count, index;

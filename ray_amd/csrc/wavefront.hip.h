@@ -190,10 +190,10 @@ struct DeferredSoA {
 };
 
 struct PixelBuffers {
-    float4 *temp; // [layers][h][w]: radiance of the iteration(s) in flight
+    float4 *temp; // the virtual frame of the pass (Layering, rt_base.h): radiance of the iteration(s) in flight
     float4 *full, *half, *raw, *final_, *base_color, *depth_normals;
     uint16_t *required_samples;
-    float4 *aux_base_layers, *aux_dn_layers; // [layers][h][w], batched passes only (rt_pixel.h)
+    float4 *aux_base_layers, *aux_dn_layers; // the same virtual frame, batched passes only (rt_pixel.h)
     float4 *variance; // [h][w]: the variance estimate of the last accumulate (the reference leaves it in its temp buffer,
                       // RendererCPU.h:641-645; DenoiseImage reads it from there)
 };
