@@ -37,11 +37,13 @@
 #include "scene_update.h"
 #include "scene_validate.h"
 #include "sort.h"
+#include "trace_select.h"
 
 using namespace rt;
 
 // the host side, in parts (one translation unit with the kernels above: templates and launch sites see each other)
 #include "rayhip_ctx.hip.h"
+#include "rayhip_trace.hip.h"
 #include "rayhip_deform.hip.h"
 #include "rayhip_upload.hip.h"
 #include "rayhip_render.hip.h"

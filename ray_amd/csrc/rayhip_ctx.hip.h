@@ -78,14 +78,7 @@ struct rayhip_ctx {
     bool plain_ior = false; // no material of the scene refracts: ShadeParams::plain_ior for the passes that start at the camera
     hipDeviceProp_t props = {};
     int grid_waves = 0; // resident-ish grid for the wave-per-block kernels
-    bool small_scene = false; // BLAS nodes + triangles fit one XCD's L2: traversal kernels with the smaller register footprint
-    int refill_waves = 0; // largest grid of the persistent closest-hit kernel (blocks); 0 = kernel switched off
-    int refill_resident = 0; // ... and the number of its blocks the device holds at once
-    int refill_resident4 = 0; // ... of its 4-wide form (the grid of a launch whose chunks are handed out dynamically)
     int sort_key_mode = 0; // RAYHIP_SORT_KEY (tuning, rt_sort.h)
-    // RAYHIP_PRIMARY_WAVES / RAYHIP_SHADOW_WAVES: register footprint of the plain K2 (primary rays) / of K3.  K3 runs at 5 waves per
-    // SIMD (96 VGPRs, 32 spilled registers per ray instead of 51 at 6 waves: same time, a third less scratch traffic)
-    int tune_primary_waves = 0, tune_shadow_waves = 5;
     // layered passes: a primary wavefront holds S samples of each of 64 / S pixels of an 8x8 tile (RayGenTiling); the S rays of a pixel walk the
     // same nodes, hit the same triangle and read the same material.  Measured on the headline scene, ms per 64-spp frame, S = 4 / 16 / 64
     // (profiles/layer_layout/README.md): primary K2 13.9 / 13.1 / 12.6 whatever the layout; the primary shade 12.4 / 16.0 / 23.0 while whole
@@ -95,16 +88,9 @@ struct rayhip_ctx {
     // how the layers of a pass lie in the per-iteration pixel buffers (Layering, rt_base.h): 1 = a pixel's layers adjacent, 0 = whole
     // layers side by side.  RAYHIP_LAYER_LAYOUT
     int layer_layout = 1;
-    bool shadow_refill = true; // K3 as the flat persistent kernel (4-wide walk); RAYHIP_SHADOW_REFILL=0: the nested form
-    bool refill_secondary_only = false; // RAYHIP_REFILL=2: primary rays (coherent, every lane busy to the end) keep the plain kernel
-    bool refill_primary_whole = false;  // RAYHIP_REFILL=3: ... or take the flat kernel with whole-chunk refills (no spill stores in the walk)
-    bool refill_pool = false;           // RAYHIP_REFILL=4: 3 + the secondary bounces of 4-wide scenes through the pooled kernel (k_trace_closest_pool)
-    int pool_waves = 0, pool_resident = 0; // its grid
-    bool pool_scene = false;               // ... and whether the scene in place suits it (refresh_scene_view)
-    bool direct_entry = true;  // RAYHIP_DIRECT_ENTRY=0: one-instance scenes walk their top level like any other (kernels_closest_refill.hip.h: DIRECT)
-    bool direct_scene = false; // ... whether the scene in place has ONE instance over the 4-wide tree, SceneView::direct filled (refresh_top_level_view)
+    TraceConfig trace; // which K2 / K3 kernels the passes and the hooks launch, and their grids (trace_select.h; init_trace_config below)
     // the direct-entry form of the persistent walks replaces the generic one in every launch of them
-    bool direct() const { return wide == 4 && direct_entry && direct_scene && sc.direct.on != 0u; }
+    bool direct() const { return wide == 4 && trace.direct_entry && trace.direct_scene && sc.direct.on != 0u; }
 
     DevBuf pmj, filter_table;
     // scene
@@ -263,7 +249,6 @@ struct rayhip_ctx {
     uint32_t work_cursor = 0, work_cleared = 0;
     bool dynamic_chunks = false;
     int dyn_mult = 1;        // blocks per resident wave slot of a dynamic launch (RAYHIP_DYN_MULT)
-    int shadow_resident = 0; // blocks of k_trace_shadow_refill the device holds at once
     uint32_t *next_work() {
         if (!dynamic_chunks || work_cursor >= work_cleared) {
             return nullptr; // (a launch without a counter walks statically)
@@ -330,7 +315,6 @@ struct rayhip_ctx {
     hipStream_t stream2 = nullptr;
     hipEvent_t fork_event = nullptr, join_event = nullptr;
     DevBuf stack_spill2; // K3's own overflow slabs while it runs next to K2
-    bool overlap_shadow = true;
     struct Interval { // a timed launch on the second stream (resolve_timing)
         size_t ev0, ev1;
         int stage, trav;
@@ -594,6 +578,146 @@ void rays_to_soa(const rayhip_ray *in, int n, std::vector<float4> pl[4], std::ve
         xd[i] = make_uint2(r.xy, r.depth);
     }
 }
+
+// ---- what the kernel-level hooks (rayhip_hooks.hip.h) share: the SoA planes of rays and hits on the host, their copies to and from the
+// device on the context stream (the caller synchronises), the traversal counters around one launch.  The host arrays belong to the caller
+// and outlive the copies.
+struct HostRays {
+    std::vector<float4> pl[4];
+    std::vector<uint2> xd;
+};
+struct HostHits {
+    std::vector<float4> hp;
+    std::vector<float> hv;
+};
+int upload_rays(rayhip_ctx *c, const rayhip_ray *rays, int count, HostRays &h) {
+    rays_to_soa(rays, count, h.pl, h.xd);
+    for (int k = 0; k < 4; ++k) {
+        HIP_TRY(hipMemcpyAsync(c->ray_planes[0][k].p, h.pl[k].data(), size_t(count) * 16, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(c->ray_planes[0][4].p, h.xd.data(), size_t(count) * 8, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+int upload_hits(rayhip_ctx *c, const rayhip_hit *hits, int count, HostHits &h) {
+    h.hp.resize(size_t(count)), h.hv.resize(size_t(count));
+    for (int i = 0; i < count; ++i) {
+        float oi, pi;
+        memcpy(&oi, &hits[i].obj_index, 4), memcpy(&pi, &hits[i].prim_index, 4);
+        h.hp[i] = make_float4(oi, pi, hits[i].t, hits[i].u);
+        h.hv[i] = hits[i].v;
+    }
+    HIP_TRY(hipMemcpyAsync(c->hit_planes[0].p, h.hp.data(), size_t(count) * 16, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->hit_planes[1].p, h.hv.data(), size_t(count) * 4, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+// the first `n` rays of ray buffer `buf`: the 16-byte planes first .. last, then the pixel | depth plane
+int download_rays(rayhip_ctx *c, int buf, size_t n, HostRays &h, int first = 0, int last = 3) {
+    for (int k = first; k <= last; ++k) {
+        h.pl[k].resize(n);
+        HIP_TRY(hipMemcpyAsync(h.pl[k].data(), c->ray_planes[buf][k].p, n * 16, hipMemcpyDeviceToHost, c->stream));
+    }
+    h.xd.resize(n);
+    HIP_TRY(hipMemcpyAsync(h.xd.data(), c->ray_planes[buf][4].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+int download_hits(rayhip_ctx *c, size_t n, HostHits &h) {
+    h.hp.resize(n), h.hv.resize(n);
+    HIP_TRY(hipMemcpyAsync(h.hp.data(), c->hit_planes[0].p, n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h.hv.data(), c->hit_planes[1].p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+void rays_from_soa(const HostRays &h, size_t n, rayhip_ray *out) {
+    for (size_t i = 0; i < n; ++i) {
+        rayhip_ray &r = out[i];
+        r.o[0] = h.pl[0][i].x, r.o[1] = h.pl[0][i].y, r.o[2] = h.pl[0][i].z, r.pdf = h.pl[0][i].w;
+        r.d[0] = h.pl[1][i].x, r.d[1] = h.pl[1][i].y, r.d[2] = h.pl[1][i].z, r.cone_width = h.pl[1][i].w;
+        r.c[0] = h.pl[2][i].x, r.c[1] = h.pl[2][i].y, r.c[2] = h.pl[2][i].z, r.cone_spread = h.pl[2][i].w;
+        r.ior[0] = h.pl[3][i].x, r.ior[1] = h.pl[3][i].y, r.ior[2] = h.pl[3][i].z, r.ior[3] = h.pl[3][i].w;
+        r.xy = h.xd[i].x, r.depth = h.xd[i].y;
+    }
+}
+void hits_from_soa(const HostHits &h, size_t n, rayhip_hit *out) {
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(&out[i].obj_index, &h.hp[i].x, 4), memcpy(&out[i].prim_index, &h.hp[i].y, 4);
+        out[i].t = h.hp[i].z, out[i].u = h.hp[i].w, out[i].v = h.hv[i];
+    }
+}
+// one launch's own traversal counters: `tc` (K2's or K3's TRAV_COUNTER_WORDS words) is saved and zeroed before the launch ...
+struct CounterScope {
+    unsigned long long before[TRAV_COUNTER_WORDS], after[TRAV_COUNTER_WORDS];
+};
+int counters_begin(rayhip_ctx *c, unsigned long long *tc, CounterScope &k) {
+    HIP_TRY(hipMemcpyAsync(k.before, tc, sizeof(k.before), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(tc, 0, sizeof(k.before), c->stream));
+    return 0;
+}
+// ... read and put back after it (the launch is through: the caller has synchronised), and handed to the caller if it asked
+int counters_end(rayhip_ctx *c, unsigned long long *tc, CounterScope &k, rayhip_trav_counters *out) {
+    HIP_TRY(hipMemcpyAsync(k.after, tc, sizeof(k.after), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(tc, k.before, sizeof(k.before), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (out) {
+        out->rays = k.after[0], out->nodes = k.after[1];
+        out->tris = k.after[2], out->instances = k.after[3];
+        out->max_stack = k.after[4], out->nodes4 = k.after[5];
+    }
+    return 0;
+}
+
+// rayhip_ctx::trace from the environment and the device (trace_select.h lists the variables); `per_cu`: resident blocks per CU of the
+// plain closest-hit kernel, the fallback of every occupancy query below.  grid_waves is set.
+void init_trace_config(rayhip_ctx *c, const int per_cu) {
+    TraceConfig &t = c->trace;
+    const int cus = c->props.multiProcessorCount;
+    auto env_int = [](const char *name, int otherwise) {
+        const char *e = getenv(name);
+        return e ? atoi(e) : otherwise;
+    };
+    t.overlap_shadow = env_int("RAYHIP_OVERLAP_SHADOW", 1) != 0;
+    t.tune_primary_waves = env_int("RAYHIP_PRIMARY_WAVES", t.tune_primary_waves);
+    t.tune_shadow_waves = env_int("RAYHIP_SHADOW_WAVES", t.tune_shadow_waves);
+    t.shadow_refill = env_int("RAYHIP_SHADOW_REFILL", 1) != 0;
+    t.direct_entry = env_int("RAYHIP_DIRECT_ENTRY", 1) != 0;
+    // The persistent ray-refill form of the closest-hit kernel (kernels_closest_refill.hip.h): lanes whose ray is finished fetch the next one
+    // instead of idling until the longest walk of their wavefront ends.  RAYHIP_REFILL: 2 = for the secondary
+    // bounces (incoherent rays, 45 % of the lane slots of the plain kernel belong to finished rays: K2 2.25 -> 2.05 ms per
+    // iteration on the Bistro-class scene), the coherent primary rays keep the plain kernel (refill: 0.52 vs 0.35 ms);
+    // 1 = every bounce; 0 = off.  The grid is RAYHIP_REFILL_MULT (default 16) blocks per resident wave slot: with exactly
+    // one block per slot the launch ends on its slowest wavefront (1x: 1.84, 4x: 1.79, 16x: 1.74 ms; 64x the same).
+    // Scenes that fit L2 gain too (03_principled 2048^2: 965 -> 994 Msamples/s, Cornell 1024^2: 1056 -> 1064).
+    // 3 (default): the secondary bounces refill lane by lane; the coherent primary rays run the same flat kernel but take their
+    // chunks whole (the plain kernel's schedule without its 60 spilled registers per ray: 2.13 vs 2.10 ms per iteration for
+    // K2, 7.8 GB fewer scratch writes per primary launch)
+    const int mode = env_int("RAYHIP_REFILL", 3);
+    if (mode != 0) {
+        int per_cu_refill = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_refill, k_trace_closest_refill<8>, WAVE, 0) != hipSuccess || per_cu_refill <= 0) {
+            per_cu_refill = per_cu;
+        }
+        const int refill_mult = std::max(1, std::min(64, env_int("RAYHIP_REFILL_MULT", 16)));
+        t.refill_resident = cus * per_cu_refill;
+        int per_cu4 = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, k_trace_closest_refill<4>, WAVE, 0) != hipSuccess || per_cu4 <= 0) {
+            per_cu4 = per_cu_refill;
+        }
+        t.refill_resident4 = cus * per_cu4;
+        t.refill_waves = std::min(c->grid_waves, t.refill_resident * refill_mult);
+        set_refill_mode(t, mode);
+        if (t.refill_pool) {
+            int per_cu_pool = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_pool, k_trace_closest_pool<>, WAVE, 0) != hipSuccess || per_cu_pool <= 0) {
+                per_cu_pool = per_cu_refill;
+            }
+            t.pool_resident = cus * per_cu_pool;
+            t.pool_waves = std::min(c->grid_waves, t.pool_resident * refill_mult);
+        }
+    }
+    int per_cu_shadow = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_shadow, k_trace_shadow_refill<>, WAVE, 0) != hipSuccess || per_cu_shadow <= 0) {
+        per_cu_shadow = per_cu;
+    }
+    t.shadow_resident = cus * per_cu_shadow;
+}
 } // namespace
 
 extern "C" {
@@ -626,16 +750,6 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
         return fail("failed to initialise HIP device %d", device);
     }
     g_touch_stream = c->stream;
-    if (const char *e = getenv("RAYHIP_OVERLAP_SHADOW")) {
-        c->overlap_shadow = atoi(e) != 0;
-    }
-    if (c->overlap_shadow) {
-        int least = 0, greatest = 0; // (numerically: greatest priority <= least priority)
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, least) != hipSuccess ||
-            hipEventCreateWithFlags(&c->fork_event, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->join_event, hipEventDisableTiming) != hipSuccess) {
-            c->overlap_shadow = false;
-        }
-    }
     // persistent grid of the wave-per-block kernels: as many blocks as are resident (LDS stack + VGPR budget)
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_closest<false, 8>, WAVE, 0) != hipSuccess || per_cu <= 0) {
@@ -652,11 +766,13 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
         }
     }
     c->grid_waves = c->props.multiProcessorCount * per_cu * grid_mult;
-    if (const char *e = getenv("RAYHIP_PRIMARY_WAVES")) {
-        c->tune_primary_waves = atoi(e);
-    }
-    if (const char *e = getenv("RAYHIP_SHADOW_WAVES")) {
-        c->tune_shadow_waves = atoi(e);
+    init_trace_config(c, per_cu);
+    if (c->trace.overlap_shadow) { // (before the spill slabs below are sized, and long before a pass forks)
+        int least = 0, greatest = 0; // (numerically: greatest priority <= least priority)
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, least) != hipSuccess ||
+            hipEventCreateWithFlags(&c->fork_event, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->join_event, hipEventDisableTiming) != hipSuccess) {
+            c->trace.overlap_shadow = false;
+        }
     }
     if (const char *e = getenv("RAYHIP_RAYGEN_SAMPLES")) {
         const int v = atoi(e);
@@ -664,9 +780,6 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
     }
     if (const char *e = getenv("RAYHIP_LAYER_LAYOUT")) {
         c->layer_layout = atoi(e) != 0 ? 1 : 0;
-    }
-    if (const char *e = getenv("RAYHIP_SHADOW_REFILL")) {
-        c->shadow_refill = atoi(e) != 0;
     }
     if (const char *e = getenv("RAYHIP_SORT_KEY")) {
         c->sort_key_mode = std::max(0, std::min(3, atoi(e)));
@@ -693,55 +806,9 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
     if (const char *e = getenv("RAYHIP_SHADE_LDS_INSTANCES_MAX")) {
         c->shade_lds_instances_max = uint32_t(std::max(0, atoi(e)));
     }
-    // The persistent ray-refill form of the closest-hit kernel (kernels_closest_refill.hip.h): lanes whose ray is finished fetch the next one
-    // instead of idling until the longest walk of their wavefront ends.  RAYHIP_REFILL: 2 = for the secondary
-    // bounces (incoherent rays, 45 % of the lane slots of the plain kernel belong to finished rays: K2 2.25 -> 2.05 ms per
-    // iteration on the Bistro-class scene), the coherent primary rays keep the plain kernel (refill: 0.52 vs 0.35 ms);
-    // 1 = every bounce; 0 = off.  The grid is RAYHIP_REFILL_MULT (default 16) blocks per resident wave slot: with exactly
-    // one block per slot the launch ends on its slowest wavefront (1x: 1.84, 4x: 1.79, 16x: 1.74 ms; 64x the same).
-    // Scenes that fit L2 gain too (03_principled 2048^2: 965 -> 994 Msamples/s, Cornell 1024^2: 1056 -> 1064).
-    {
-        // 3 (default): the secondary bounces refill lane by lane; the coherent primary rays run the same flat kernel but take their
-        // chunks whole (the plain kernel's schedule without its 60 spilled registers per ray: 2.13 vs 2.10 ms per iteration for
-        // K2, 7.8 GB fewer scratch writes per primary launch)
-        const int mode = getenv("RAYHIP_REFILL") != nullptr ? atoi(getenv("RAYHIP_REFILL")) : 3;
-        if (const char *e = getenv("RAYHIP_DIRECT_ENTRY")) {
-            c->direct_entry = atoi(e) != 0;
-        }
-        if (mode != 0) {
-            int per_cu_refill = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_refill, k_trace_closest_refill<8>, WAVE, 0) != hipSuccess || per_cu_refill <= 0) {
-                per_cu_refill = per_cu;
-            }
-            int refill_mult = 16;
-            if (const char *e = getenv("RAYHIP_REFILL_MULT")) {
-                refill_mult = std::max(1, std::min(64, atoi(e)));
-            }
-            c->refill_resident = c->props.multiProcessorCount * per_cu_refill;
-            {
-                int per_cu4 = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, k_trace_closest_refill<4>, WAVE, 0) != hipSuccess || per_cu4 <= 0) {
-                    per_cu4 = per_cu_refill;
-                }
-                c->refill_resident4 = c->props.multiProcessorCount * per_cu4;
-            }
-            c->refill_waves = std::min(c->grid_waves, c->refill_resident * refill_mult);
-            c->refill_secondary_only = mode == 2 || mode == 3 || mode == 4;
-            c->refill_primary_whole = mode == 3 || mode == 4;
-            if (mode == 4) {
-                int per_cu_pool = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_pool, k_trace_closest_pool<>, WAVE, 0) != hipSuccess || per_cu_pool <= 0) {
-                    per_cu_pool = per_cu_refill;
-                }
-                c->refill_pool = true;
-                c->pool_resident = c->props.multiProcessorCount * per_cu_pool;
-                c->pool_waves = std::min(c->grid_waves, c->pool_resident * refill_mult);
-            }
-        }
-    }
     // (sized for the shallowest LDS stack any kernel keeps: the pooled closest-hit kernel trades stack entries for its pool)
     if (c->stack_spill.alloc(size_t(c->grid_waves) * std::max(STACK_SPILL_DEPTH * WAVE, POOL_SLAB_WORDS) * sizeof(uint32_t)) ||
-        (c->overlap_shadow && c->stack_spill2.alloc(size_t(c->grid_waves) * size_t(STACK_SPILL_DEPTH * WAVE) * sizeof(uint32_t)))) {
+        (c->trace.overlap_shadow && c->stack_spill2.alloc(size_t(c->grid_waves) * size_t(STACK_SPILL_DEPTH * WAVE) * sizeof(uint32_t)))) {
         delete c;
         return 1;
     }
@@ -777,13 +844,6 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
             memset(hp, 0, bytes);
             c->census.assign(size_t(MAX_BOUNCE_SLOTS) * rayhip_ctx::QUEUES_PER_BOUNCE, 0.0f);
         }
-    }
-    {
-        int per_cu_shadow = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_shadow, k_trace_shadow_refill<>, WAVE, 0) != hipSuccess || per_cu_shadow <= 0) {
-            per_cu_shadow = per_cu;
-        }
-        c->shadow_resident = c->props.multiProcessorCount * per_cu_shadow;
     }
     (void)hipMemsetAsync(c->trav_counters.p, 0, sizeof(unsigned long long) * 2 * TRAV_COUNTER_WORDS, c->stream);
     // the stage stopwatch's events exist up front: creating them lazily put ~30 ms of runtime initialisation into the first

@@ -288,7 +288,7 @@ static int refit_after_vertices(rayhip_ctx *c, VertexStamps st) {
                 return fail("4-wide collapse failed: %s", why.c_str());
             }
             // a box the grid cannot hold: the kernels walk the BVH2 from here on, as after an upload of such a scene
-            c->wide = 0, c->small_scene = false;
+            c->wide = 0, c->trace.small_scene = false;
             c->sc.nodes4 = nullptr, c->sc.blas_root4 = nullptr;
             for (auto &ref : c->mesh_refs) {
                 ref.second.root4 = 0;

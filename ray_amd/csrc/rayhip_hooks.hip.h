@@ -26,28 +26,14 @@ int rayhip_k_generate_primary_rays(rayhip_ctx *c, const rayhip_camera *cam, cons
     uint32_t n = 0;
     HIP_TRY(hipMemcpyAsync(&n, c->ray_count(0), 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    std::vector<float4> pl[4], hp(n);
-    std::vector<uint2> xd(n);
-    std::vector<float> hv(n);
-    for (int k = 0; k < 4; ++k) {
-        pl[k].resize(n);
-        HIP_TRY(hipMemcpyAsync(pl[k].data(), c->ray_planes[0][k].p, size_t(n) * 16, hipMemcpyDeviceToHost, s));
+    HostRays hr;
+    HostHits hh;
+    if (download_rays(c, 0, n, hr) || download_hits(c, n, hh)) {
+        return 1;
     }
-    HIP_TRY(hipMemcpyAsync(xd.data(), c->ray_planes[0][4].p, size_t(n) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(hp.data(), c->hit_planes[0].p, size_t(n) * 16, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(hv.data(), c->hit_planes[1].p, size_t(n) * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    for (uint32_t i = 0; i < n; ++i) {
-        rayhip_ray &r = out_rays[i];
-        r.o[0] = pl[0][i].x, r.o[1] = pl[0][i].y, r.o[2] = pl[0][i].z, r.pdf = pl[0][i].w;
-        r.d[0] = pl[1][i].x, r.d[1] = pl[1][i].y, r.d[2] = pl[1][i].z, r.cone_width = pl[1][i].w;
-        r.c[0] = pl[2][i].x, r.c[1] = pl[2][i].y, r.c[2] = pl[2][i].z, r.cone_spread = pl[2][i].w;
-        r.ior[0] = pl[3][i].x, r.ior[1] = pl[3][i].y, r.ior[2] = pl[3][i].z, r.ior[3] = pl[3][i].w;
-        r.xy = xd[i].x, r.depth = xd[i].y;
-        rayhip_hit &h = out_hits[i];
-        memcpy(&h.obj_index, &hp[i].x, 4), memcpy(&h.prim_index, &hp[i].y, 4);
-        h.t = hp[i].z, h.u = hp[i].w, h.v = hv[i];
-    }
+    rays_from_soa(hr, n, out_rays);
+    hits_from_soa(hh, n, out_hits);
     *out_count = int(n);
     return 0;
 }
@@ -64,80 +50,44 @@ int rayhip_k_intersect_closest(rayhip_ctx *c, const rayhip_camera *cam, rayhip_r
         return fail("ray count exceeds the wavefront buffers (w*h)");
     }
     hipStream_t s = c->stream;
-    std::vector<float4> pl[4], hp;
-    hp.resize(size_t(count));
-    std::vector<uint2> xd;
-    std::vector<float> hv{};
-    hv.resize(size_t(count));
-    rays_to_soa(rays, count, pl, xd);
-    for (int i = 0; i < count; ++i) {
-        float oi, pi;
-        memcpy(&oi, &hits[i].obj_index, 4), memcpy(&pi, &hits[i].prim_index, 4);
-        hp[i] = make_float4(oi, pi, hits[i].t, hits[i].u);
-        hv[i] = hits[i].v;
+    HostRays hr;
+    HostHits hh;
+    if (upload_rays(c, rays, count, hr) || upload_hits(c, hits, count, hh)) {
+        return 1;
     }
-    for (int k = 0; k < 4; ++k) {
-        HIP_TRY(hipMemcpyAsync(c->ray_planes[0][k].p, pl[k].data(), size_t(count) * 16, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipMemcpyAsync(c->ray_planes[0][4].p, xd.data(), size_t(count) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->hit_planes[0].p, hp.data(), size_t(count) * 16, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->hit_planes[1].p, hv.data(), size_t(count) * 4, hipMemcpyHostToDevice, s));
     const uint32_t n = uint32_t(count);
     HIP_TRY(hipMemcpyAsync(c->ray_count(0), &n, 4, hipMemcpyHostToDevice, s));
     unsigned long long *tc = c->trav_counters.as<unsigned long long>();
-    unsigned long long before[TRAV_COUNTER_WORDS], after[TRAV_COUNTER_WORDS];
-    HIP_TRY(hipMemcpyAsync(before, tc, sizeof(before), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemsetAsync(tc, 0, sizeof(before), s));
+    CounterScope ks;
+    if (counters_begin(c, tc, ks)) {
+        return 1;
+    }
     const TraceParams tp = make_trace_params(*cam, c->sc.tlas_root, iteration);
     const int g = int(std::min<size_t>(size_t(c->grid_waves), (size_t(count) + WAVE - 1) / WAVE));
     const RayQueue q = c->ray_queue(0, size_t(count), 1);
     {
-        const int gg = g ? g : 1;
-#define KK_ARGS c->sc, tp, c->rays[0], c->hits, q, 0, c->stack_spill.as<uint32_t>(), tc, single_layer(c->w, c->h)
-        if ((flags & RAYHIP_FLAG_COUNT_WIDE) && c->wide == 8) { // the product walk with counters
-            k_trace_closest<true, 8><<<gg, WAVE, 0, s>>>(KK_ARGS);
-        } else if ((flags & RAYHIP_FLAG_COUNT_WIDE) && c->wide == 4) {
-            k_trace_closest<true, 4><<<gg, WAVE, 0, s>>>(KK_ARGS);
-        } else if (flags & RAYHIP_FLAG_COUNT_TRAVERSAL) { // instrumented walk of the reference's BVH2
-            k_trace_closest<true, 0><<<gg, WAVE, 0, s>>>(KK_ARGS);
-        } else if (c->wide == 4 && c->refill_pool && c->pool_scene) { // what rayhip_render launches (the pooled form also takes preset hits)
-            k_trace_closest_pool<><<<std::max(1, std::min(g, c->pool_waves)), WAVE, 0, s>>>(c->sc, tp, c->rays[0], c->hits, q, 0, c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h));
-        } else if (c->wide == 8 && c->refill_waves) {
-            k_trace_closest_refill<8><<<std::max(1, std::min(g, c->refill_waves)), WAVE, 0, s>>>(c->sc, tp, c->rays[0], c->hits, q, 0, c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
-        } else if (c->wide == 4 && c->refill_waves && c->direct()) {
-            k_trace_closest_refill<4, RT_REFILL_MIN_DIRECT, true><<<std::max(1, std::min(g, c->refill_waves)), WAVE, 0, s>>>(c->sc, tp, c->rays[0], c->hits, q, 0, c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
-        } else if (c->wide == 4 && c->refill_waves) {
-            k_trace_closest_refill<4><<<std::max(1, std::min(g, c->refill_waves)), WAVE, 0, s>>>(c->sc, tp, c->rays[0], c->hits, q, 0, c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
-        } else if (c->wide == 8) {
-            k_trace_closest<false, 8><<<gg, WAVE, 0, s>>>(KK_ARGS);
-        } else if (c->wide == 4) {
-            k_trace_closest<false, 4><<<gg, WAVE, 0, s>>>(KK_ARGS);
-        } else {
-            k_trace_closest<false, 0><<<gg, WAVE, 0, s>>>(KK_ARGS);
-        }
-#undef KK_ARGS
+        // "the kernel the passes launch", in the hook's reading of the knobs (trace_select.h: TraceRole::Hook)
+        const ClosestForm form = closest_form(c->trace, c->wide, c->direct(), TraceRole::Hook, flags);
+        ClosestLaunch a;
+        a.sc = c->sc, a.tp = tp, a.rays = c->rays[0], a.hits = c->hits, a.queue = q, a.init_hits = 0; // (the pooled form also takes preset hits)
+        a.spill = c->stack_spill.as<uint32_t>(), a.counters = tc, a.layers = single_layer(c->w, c->h);
+        const int grid = form == ClosestForm::Pooled ? std::min(g, c->trace.pool_waves) : is_lane(form) ? std::min(g, c->trace.refill_waves) : g;
+        launch_closest(form, std::max(1, grid), s, a);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpyAsync(after, tc, sizeof(after), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(tc, before, sizeof(before), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (out_counters) {
-        out_counters->rays = after[0], out_counters->nodes = after[1];
-        out_counters->tris = after[2], out_counters->instances = after[3];
-        out_counters->max_stack = after[4], out_counters->nodes4 = after[5];
+    if (counters_end(c, tc, ks, out_counters)) {
+        return 1;
     }
-    HIP_TRY(hipMemcpyAsync(pl[2].data(), c->ray_planes[0][2].p, size_t(count) * 16, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(xd.data(), c->ray_planes[0][4].p, size_t(count) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(hp.data(), c->hit_planes[0].p, size_t(count) * 16, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(hv.data(), c->hit_planes[1].p, size_t(count) * 4, hipMemcpyDeviceToHost, s));
+    if (download_rays(c, 0, size_t(count), hr, 2, 2) || download_hits(c, size_t(count), hh)) { // (of a ray the walk changes throughput and depth)
+        return 1;
+    }
     HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < count; ++i) {
-        rays[i].c[0] = pl[2][i].x, rays[i].c[1] = pl[2][i].y, rays[i].c[2] = pl[2][i].z;
-        rays[i].depth = xd[i].y;
-        memcpy(&hits[i].obj_index, &hp[i].x, 4), memcpy(&hits[i].prim_index, &hp[i].y, 4);
-        hits[i].t = hp[i].z, hits[i].u = hp[i].w, hits[i].v = hv[i];
+        rays[i].c[0] = hr.pl[2][i].x, rays[i].c[1] = hr.pl[2][i].y, rays[i].c[2] = hr.pl[2][i].z;
+        rays[i].depth = hr.xd[i].y;
     }
+    hits_from_soa(hh, size_t(count), hits);
     return 0;
 }
 
@@ -170,31 +120,27 @@ int rayhip_k_intersect_shadow(rayhip_ctx *c, const rayhip_camera *cam, const ray
     const uint32_t n = uint32_t(count);
     HIP_TRY(hipMemcpyAsync(c->shadow_count(0), &n, 4, hipMemcpyHostToDevice, s));
     unsigned long long *tc = c->trav_counters.as<unsigned long long>() + TRAV_COUNTER_WORDS;
-    unsigned long long before[TRAV_COUNTER_WORDS], after[TRAV_COUNTER_WORDS];
-    HIP_TRY(hipMemcpyAsync(before, tc, sizeof(before), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemsetAsync(tc, 0, sizeof(before), s));
+    CounterScope ks;
+    if (counters_begin(c, tc, ks)) {
+        return 1;
+    }
     const TraceParams tp = make_trace_params(*cam, c->sc.tlas_root, iteration);
     const int g = int(std::min<size_t>(size_t(c->grid_waves), (size_t(count) + WAVE - 1) / WAVE));
-    // results land in the (otherwise idle) hit plane
-    if (getenv("RAYHIP_HOOK_SHADOW_REFILL") && c->wide == 4 && c->direct()) { // ... its direct-entry form, where the passes launch that
-        k_trace_shadow_refill<RT_SHADOW_REFILL_MIN_DIRECT, true><<<g ? g : 1, WAVE, 0, s>>>(c->sc, tp, c->shadow, c->shadow_queue(0, size_t(count), 1), FLT_MAX, c->w, c->px.temp,
-                                                                                         c->hit_planes[0].as<float4>(), c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
-    } else if (getenv("RAYHIP_HOOK_SHADOW_REFILL") && c->wide == 4) { // the product's flat persistent form over the 4-wide tree (no counters)
-        k_trace_shadow_refill<<<g ? g : 1, WAVE, 0, s>>>(c->sc, tp, c->shadow, c->shadow_queue(0, size_t(count), 1), FLT_MAX, c->w, c->px.temp,
-                                                       c->hit_planes[0].as<float4>(), c->stack_spill.as<uint32_t>(), single_layer(c->w, c->h), nullptr);
-    } else {
-        k_trace_shadow<true, 0><<<g ? g : 1, WAVE, 0, s>>>(c->sc, tp, c->shadow, c->shadow_queue(0, size_t(count), 1), FLT_MAX, c->w, c->px.temp,
-                                                        c->hit_planes[0].as<float4>(), c->stack_spill.as<uint32_t>(), tc, single_layer(c->w, c->h));
+    {
+        // RAYHIP_HOOK_SHADOW_REFILL (read at every call): the product's flat persistent form over the 4-wide tree, in its direct-entry form where
+        // the passes launch that (no counters); otherwise the instrumented walk of the reference's BVH2
+        const ShadowForm form = shadow_form(c->trace, c->wide, c->direct(), TraceRole::Hook, 0u, getenv("RAYHIP_HOOK_SHADOW_REFILL") != nullptr);
+        ShadowLaunch a;
+        a.sc = c->sc, a.tp = tp, a.shadow = c->shadow, a.queue = c->shadow_queue(0, size_t(count), 1);
+        a.limit = FLT_MAX, a.pitch = c->w, a.temp = c->px.temp;
+        a.out_rc = c->hit_planes[0].as<float4>(); // results land in the (otherwise idle) hit plane
+        a.spill = c->stack_spill.as<uint32_t>(), a.counters = tc, a.layers = single_layer(c->w, c->h);
+        launch_shadow(form, g ? g : 1, s, a);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpyAsync(after, tc, sizeof(after), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(tc, before, sizeof(before), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (out_counters) {
-        out_counters->rays = after[0], out_counters->nodes = after[1];
-        out_counters->tris = after[2], out_counters->instances = after[3];
-        out_counters->max_stack = after[4], out_counters->nodes4 = after[5];
+    if (counters_end(c, tc, ks, out_counters)) {
+        return 1;
     }
     HIP_TRY(hipMemcpyAsync(out_rc, c->hit_planes[0].p, size_t(count) * 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -218,22 +164,11 @@ int rayhip_k_shade(rayhip_ctx *c, const rayhip_camera *cam, int bounce, int iter
     }
     hipStream_t s = c->stream;
     const size_t npix = size_t(c->w) * size_t(c->h);
-    std::vector<float4> pl[4], hp(static_cast<size_t>(count));
-    std::vector<uint2> xd;
-    std::vector<float> hv(static_cast<size_t>(count));
-    rays_to_soa(rays, count, pl, xd);
-    for (int i = 0; i < count; ++i) {
-        float oi, pi;
-        memcpy(&oi, &hits[i].obj_index, 4), memcpy(&pi, &hits[i].prim_index, 4);
-        hp[i] = make_float4(oi, pi, hits[i].t, hits[i].u);
-        hv[i] = hits[i].v;
+    HostRays hr;
+    HostHits hh;
+    if (upload_rays(c, rays, count, hr) || upload_hits(c, hits, count, hh)) {
+        return 1;
     }
-    for (int k = 0; k < 4; ++k) {
-        HIP_TRY(hipMemcpyAsync(c->ray_planes[0][k].p, pl[k].data(), size_t(count) * 16, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipMemcpyAsync(c->ray_planes[0][4].p, xd.data(), size_t(count) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->hit_planes[0].p, hp.data(), size_t(count) * 16, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->hit_planes[1].p, hv.data(), size_t(count) * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->px.temp, inout_color, npix * 16, hipMemcpyHostToDevice, s));
     if (c->clear_queues(bounce + 2, s)) {
         return fail("queue counter clear failed");
@@ -249,26 +184,16 @@ int rayhip_k_shade(rayhip_ctx *c, const rayhip_camera *cam, int bounce, int iter
     HIP_TRY(hipMemcpyAsync(&n_sh, c->shadow_count(bounce), 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(inout_color, c->px.temp, npix * 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    for (int k = 0; k < 4; ++k) {
-        pl[k].resize(n_sec);
-        HIP_TRY(hipMemcpyAsync(pl[k].data(), c->ray_planes[1][k].p, size_t(n_sec) * 16, hipMemcpyDeviceToHost, s));
+    if (download_rays(c, 1, n_sec, hr)) {
+        return 1;
     }
-    xd.resize(n_sec);
-    HIP_TRY(hipMemcpyAsync(xd.data(), c->ray_planes[1][4].p, size_t(n_sec) * 8, hipMemcpyDeviceToHost, s));
     std::vector<float4> sp_[3];
     for (int k = 0; k < 3; ++k) {
         sp_[k].resize(n_sh);
         HIP_TRY(hipMemcpyAsync(sp_[k].data(), c->shadow_planes[k].p, size_t(n_sh) * 16, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    for (uint32_t i = 0; i < n_sec; ++i) {
-        rayhip_ray &r = out_secondary[i];
-        r.o[0] = pl[0][i].x, r.o[1] = pl[0][i].y, r.o[2] = pl[0][i].z, r.pdf = pl[0][i].w;
-        r.d[0] = pl[1][i].x, r.d[1] = pl[1][i].y, r.d[2] = pl[1][i].z, r.cone_width = pl[1][i].w;
-        r.c[0] = pl[2][i].x, r.c[1] = pl[2][i].y, r.c[2] = pl[2][i].z, r.cone_spread = pl[2][i].w;
-        r.ior[0] = pl[3][i].x, r.ior[1] = pl[3][i].y, r.ior[2] = pl[3][i].z, r.ior[3] = pl[3][i].w;
-        r.xy = xd[i].x, r.depth = xd[i].y;
-    }
+    rays_from_soa(hr, n_sec, out_secondary);
     for (uint32_t i = 0; i < n_sh; ++i) {
         rayhip_shadow_ray &r = out_shadow[i];
         r.o[0] = sp_[0][i].x, r.o[1] = sp_[0][i].y, r.o[2] = sp_[0][i].z, memcpy(&r.depth, &sp_[0][i].w, 4);

@@ -107,7 +107,7 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
     const int gtrace = int(std::min<size_t>(size_t(gw), nslots / WAVE));
     unsigned long long *tc = c->trav_counters.as<unsigned long long>();
     uint32_t *spill = c->stack_spill.as<uint32_t>();
-    const TraceParams tp_ = make_trace_params(*cam, c->sc.tlas_root, iteration);
+    const TraceParams tp = make_trace_params(*cam, c->sc.tlas_root, iteration);
 
     // striped queues unless a stage needs one dense ray array (the sort)
     const uint32_t stripes = sort_rays ? 1u : QUEUE_MAX_STRIPES;
@@ -134,60 +134,29 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
         const uint32_t want = std::max(std::min(expect, uint32_t(std::max(resident, 1))), expect / uint32_t(c->chunks_per_block));
         return int(std::min<uint32_t>(uint32_t(full), std::max(want, 1u)));
     };
-    // K2 launcher (instrumented variant on request)
-    auto launch_closest = [&](const RaySoA &r, const RayQueue &q, int init_hits) {
-        const int wide = c->wide;
-#define K2_ARGS c->sc, tp_, r, c->hits, q, init_hits, spill, tc, layers
-        if (count_wide && wide == 8) {
-            k_trace_closest<true, 8><<<gtrace, WAVE, 0, s>>>(K2_ARGS);
-        } else if (count_wide && wide == 4) {
-            k_trace_closest<true, 4><<<gtrace, WAVE, 0, s>>>(K2_ARGS);
-        } else if (count) {
-            k_trace_closest<true, 0><<<gtrace, WAVE, 0, s>>>(K2_ARGS);
-        } else if (wide && c->refill_waves && c->refill_primary_whole && !init_hits) {
-            // primary rays (coherent): the flat kernel, chunks taken whole (RAYHIP_REFILL=3)
-            // (static walk: this launch takes a chunk every ~8 ns chip-wide, more than one counter can hand out -- wavefront.hip.h)
-            if (wide == 8) {
-                k_trace_closest_refill<8, WAVE><<<gtrace, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, nullptr);
-            } else if (c->direct()) { // one instance: entered from the kernel arguments (kernels_closest_refill.hip.h: DIRECT)
-                k_trace_closest_refill<4, WAVE, true><<<gtrace, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, nullptr);
-            } else {
-                k_trace_closest_refill<4, WAVE><<<gtrace, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, nullptr);
-            }
-        } else if (wide == 4 && c->refill_pool && c->pool_scene && init_hits) {
-            // secondary bounces, pooled kernel (grid: as for the refill kernel below)
-            const int want = int(std::min<size_t>(size_t(c->pool_waves), std::max<size_t>(size_t(c->pool_resident), nslots / WAVE / 8)));
-            k_trace_closest_pool<><<<std::min(gtrace, want), WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers);
-        } else if (wide && c->refill_waves && !(c->refill_secondary_only && !init_hits)) {
+    // K2 of one bounce: the form trace_select.h names for this role, at the grid of its family
+    auto trace_closest = [&](const RaySoA &r, const RayQueue &q, int init_hits) {
+        const ClosestForm form = closest_form(c->trace, c->wide, c->direct(), init_hits ? TraceRole::Secondary : TraceRole::Primary, flags);
+        ClosestLaunch a;
+        a.sc = c->sc, a.tp = tp, a.rays = r, a.hits = c->hits, a.queue = q, a.init_hits = init_hits;
+        a.spill = spill, a.counters = tc, a.layers = layers;
+        int grid = gtrace; // the counted, the plain and the whole-chunk forms (primary rays, coherent: RAYHIP_REFILL=3)
+        if (form == ClosestForm::Pooled) { // (grid: as for the lane-refill forms below)
+            const int want = int(std::min<size_t>(size_t(c->trace.pool_waves), std::max<size_t>(size_t(c->trace.pool_resident), nslots / WAVE / 8)));
+            grid = std::min(gtrace, want);
+        } else if (is_lane(form)) {
             // blocks: enough to even out the end of the launch (16 per wave slot on a full-size pass), but never so many that a
             // block gets fewer than ~8 chunks of 64 rays -- below that the kernel degenerates into the plain one with extra
             // set-up per block (a rank of 8 at 20 spp: 5.2 M rays per pass; 16 blocks per slot 6.6 ms, 4: 5.97, plain 5.98)
-            const int want = int(std::min<size_t>(size_t(c->refill_waves), std::max<size_t>(size_t(c->refill_resident), nslots / WAVE / 8)));
+            const int want = int(std::min<size_t>(size_t(c->trace.refill_waves), std::max<size_t>(size_t(c->trace.refill_resident), nslots / WAVE / 8)));
             // round 5: chunks handed out dynamically -- as many blocks as the device holds, every wavefront refills its lanes until the
             // queue is empty and drains once (wavefront.hip.h: ChunkWalk)
-            uint32_t *work = c->next_work();
+            a.work = c->next_work();
             const uint32_t expect = c->expect_chunks(bounce_now, 0, nslots, stripes);
-            const int resident = wide == 4 ? c->refill_resident4 : c->refill_resident;
-            const int grid = work ? dyn_grid(resident, expect) : static_grid(std::min(gtrace, want), resident, expect);
-            if (wide == 8) {
-                k_trace_closest_refill<8><<<grid, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, work);
-            } else if (c->direct()) {
-                k_trace_closest_refill<4, RT_REFILL_MIN_DIRECT, true><<<grid, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, work);
-            } else {
-                k_trace_closest_refill<4><<<grid, WAVE, 0, s>>>(c->sc, tp_, r, c->hits, q, init_hits, spill, layers, work);
-            }
-        } else if (wide == 8 && (c->small_scene || c->tune_primary_waves == 5)) {
-            k_trace_closest<false, 8, RT_TRACE_SMALL_WAVES><<<gtrace, WAVE, 0, s>>>(K2_ARGS);
-        } else if (wide == 8) {
-            k_trace_closest<false, 8><<<gtrace, WAVE, 0, s>>>(K2_ARGS);
-        } else if (wide == 4 && (c->small_scene || c->tune_primary_waves == 5)) {
-            k_trace_closest<false, 4, RT_TRACE_SMALL_WAVES><<<gtrace, WAVE, 0, s>>>(K2_ARGS);
-        } else if (wide == 4) {
-            k_trace_closest<false, 4><<<gtrace, WAVE, 0, s>>>(K2_ARGS);
-        } else {
-            k_trace_closest<false, 0><<<gtrace, WAVE, 0, s>>>(K2_ARGS);
+            const int resident = c->wide == 4 ? c->trace.refill_resident4 : c->trace.refill_resident;
+            grid = a.work ? dyn_grid(resident, expect) : static_grid(std::min(gtrace, want), resident, expect);
         }
-#undef K2_ARGS
+        launch_closest(form, grid, s, a);
     };
 
     StageTimer tm(c, stats != nullptr || (flags & RAYHIP_FLAG_TIME_STAGES) != 0);
@@ -198,7 +167,6 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
 
     RayGenParams rg = make_raygen_params(*cam, c->w, c->h, rect, iteration, c->shard);
     rg.skip_ior = c->plain_ior ? 1 : 0; // (the scatter stage will not read the plane: rayhip_upload.hip.h)
-    const TraceParams tp = make_trace_params(*cam, c->sc.tlas_root, iteration);
     const float mix_factor = 1.0f / float(iteration);
 
     const bool trace_launch = getenv("RAYHIP_TRACE_LAUNCH") != nullptr; // (diagnostics: host time of the first calls of a pass)
@@ -219,7 +187,7 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
         fprintf(stderr, "rayhip pass start (host): event record %.0f us, k_raygen launch %.0f us, event record %.0f us\n", us(h0, h1), us(h1, h2), us(h2, h3));
     }
     if (c->sc.tlas_root != 0xffffffffu) {
-        launch_closest(c->rays[0], c->ray_queue(0, nslots, stripes), 0);
+        trace_closest(c->rays[0], c->ray_queue(0, nslots, stripes), 0);
     }
     const int shade_form = c->shade_split_for_pass(); // (one form for the whole pass: rayhip_ctx.hip.h)
     int cur = 0;
@@ -257,7 +225,7 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
             if (tm.mark(ST_STRACE, 0)) {
                 return 1;
             }
-            launch_closest(c->rays[cur], c->ray_queue(bounce, nslots, stripes), 1);
+            trace_closest(c->rays[cur], c->ray_queue(bounce, nslots, stripes), 1);
             // K2's own interval ends here.  What follows -- until the shadow launch of the bounce before, which ran beside K2, is through -- is what
             // the frame spends on shadow rays beyond the trace: that wait is the shadow stage's entry in RendererBase::stats_t, so that the stages
             // PARTITION the frame again (the reference's GPU backends report exclusive intervals: RendererVK.cpp:452-487, RendererBase.h:230-244;
@@ -278,8 +246,9 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
         }
         launch_shade(c, *cam, iteration, bounce, cur, nslots, stripes, gtrace, vw, mix_factor, layers, c->plain_ior, true, shade_form);
         // K3 of this bounce: on the second stream, next to the closest-hit launch of the next bounce (rayhip_ctx: stream2), when it is the flat
-        // persistent form and nothing is being counted
-        const bool side = c->overlap_shadow && c->wide == 4 && c->shadow_refill && !count && !count_wide;
+        // persistent form (which implies that nothing is being counted)
+        const ShadowForm k3_form = shadow_form(c->trace, c->wide, c->direct(), TraceRole::Secondary, flags, false);
+        const bool side = c->trace.overlap_shadow && is_refill(k3_form);
         hipStream_t ss = side ? c->stream2 : s;
         long side_t0 = -1;
         if (side) {
@@ -292,43 +261,23 @@ static int render_pass(rayhip_ctx *c, const rayhip_camera *cam, const int rect[4
         } else if (tm.mark(bounce == 0 ? ST_PSHADOW : ST_SSHADOW, 1)) {
             return 1;
         }
-        const float limit = shadow_clamp_limit(*cam, bounce);
         if (c->sc.blocker_lights_count != 0) {
             k_shadow_blockers<<<gtrace, WAVE, 0, ss>>>(c->sc, c->shadow, c->shadow_queue(bounce, nslots, stripes));
         }
         {
-            const int wide = c->wide;
-#define K3_ARGS c->sc, tp, c->shadow, c->shadow_queue(bounce, nslots, stripes), limit, vw, c->px.temp, nullptr, spill, tc + TRAV_COUNTER_WORDS, layers
-            if (count_wide && wide == 8) {
-                k_trace_shadow<true, 8><<<gtrace, WAVE, 0, s>>>(K3_ARGS);
-            } else if (count_wide && wide == 4) {
-                k_trace_shadow<true, 4><<<gtrace, WAVE, 0, s>>>(K3_ARGS);
-            } else if (count) {
-                k_trace_shadow<true, 0><<<gtrace, WAVE, 0, s>>>(K3_ARGS);
-            } else if (wide == 4 && c->shadow_refill) { // the flat persistent form (kernels_shadow.hip.h)
-                uint32_t *work = c->next_work();
+            ShadowLaunch a;
+            a.sc = c->sc, a.tp = tp, a.shadow = c->shadow, a.queue = c->shadow_queue(bounce, nslots, stripes);
+            a.limit = shadow_clamp_limit(*cam, bounce), a.pitch = vw, a.temp = c->px.temp;
+            a.spill = spill, a.counters = tc + TRAV_COUNTER_WORDS, a.layers = layers;
+            if (is_refill(k3_form)) { // on the second stream with slabs of its own, or in line on the context stream
+                a.work = c->next_work();
                 const uint32_t expect = c->expect_chunks(bounce, 1, nslots, stripes);
-                const int grid = work ? dyn_grid(c->shadow_resident, expect) : static_grid(gtrace, c->shadow_resident, expect);
-                uint32_t *k3_spill = side ? c->stack_spill2.as<uint32_t>() : spill;
-                if (c->direct()) { // one instance: entered from the kernel arguments (kernels_shadow.hip.h: DIRECT)
-                    k_trace_shadow_refill<RT_SHADOW_REFILL_MIN_DIRECT, true><<<grid, WAVE, 0, ss>>>(c->sc, tp, c->shadow, c->shadow_queue(bounce, nslots, stripes), limit, vw,
-                                                                                                  c->px.temp, nullptr, k3_spill, layers, work);
-                } else {
-                    k_trace_shadow_refill<<<grid, WAVE, 0, ss>>>(c->sc, tp, c->shadow, c->shadow_queue(bounce, nslots, stripes), limit, vw, c->px.temp, nullptr, k3_spill,
-                                                                 layers, work);
-                }
-            } else if (wide == 8 && (c->small_scene || c->tune_shadow_waves == 5)) {
-                k_trace_shadow<false, 8, RT_TRACE_SMALL_WAVES><<<gtrace, WAVE, 0, s>>>(K3_ARGS);
-            } else if (wide == 8) {
-                k_trace_shadow<false, 8><<<gtrace, WAVE, 0, s>>>(K3_ARGS);
-            } else if (wide == 4 && (c->small_scene || c->tune_shadow_waves == 5)) {
-                k_trace_shadow<false, 4, RT_TRACE_SMALL_WAVES><<<gtrace, WAVE, 0, s>>>(K3_ARGS);
-            } else if (wide == 4) {
-                k_trace_shadow<false, 4><<<gtrace, WAVE, 0, s>>>(K3_ARGS);
-            } else {
-                k_trace_shadow<false, 0><<<gtrace, WAVE, 0, s>>>(K3_ARGS);
+                const int grid = a.work ? dyn_grid(c->trace.shadow_resident, expect) : static_grid(gtrace, c->trace.shadow_resident, expect);
+                a.spill = side ? c->stack_spill2.as<uint32_t>() : spill;
+                launch_shadow(k3_form, grid, ss, a);
+            } else { // the counted and the plain forms: always on the context stream
+                launch_shadow(k3_form, gtrace, s, a);
             }
-#undef K3_ARGS
         }
         if (side) {
             if (tm.on) {

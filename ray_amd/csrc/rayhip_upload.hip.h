@@ -170,12 +170,12 @@ static uint32_t count_top_level_instances(const rayhip_bvh2_node *nodes, const u
 static void refresh_top_level_view(rayhip_ctx *c, const uint32_t tlas_root, const rayhip_lbvh::Box &root_box, const uint32_t live_instances) {
     // the pooled closest-hit kernel hands prepared rays from lane to lane; a ray can change lanes only while nothing is pending at the top
     // level, which is every ray of a scene with ONE instance (RAYHIP_POOL_ANY=1: the pooled kernel for any scene -- tests of its other path)
-    c->pool_scene = (live_instances == 1 || getenv("RAYHIP_POOL_ANY") != nullptr) && c->instances_count < (1u << 24);
+    c->trace.pool_scene = (live_instances == 1 || getenv("RAYHIP_POOL_ANY") != nullptr) && c->instances_count < (1u << 24);
     c->sc.tlas_root = tlas_root;
     // the direct-entry form of the persistent walks (kernels_closest_refill.hip.h: DIRECT) takes the one instance from the kernel arguments:
     // its record and the root of its 4-wide tree, from the host's copies of what the device holds (rayhip_ctx::refit: the live slots and
     // the instance array of the last upload / instance update; mesh_refs: the roots, which a vertex update keeps current)
-    c->direct_scene = false;
+    c->trace.direct_scene = false;
     c->sc.direct = DirectInstance{};
     if (live_instances == 1 && tlas_root != 0xffffffffu && c->wide == 4 && c->refit.live.size() == 1 && c->refit.live[0] < c->refit.instances.size() &&
         c->refit.live[0] < c->instances_count) {
@@ -186,7 +186,7 @@ static void refresh_top_level_view(rayhip_ctx *c, const uint32_t tlas_root, cons
             memcpy(c->sc.direct.inv_xform, inst.inv_xform, sizeof(inst.inv_xform));
             c->sc.direct.ray_visibility = inst.ray_visibility;
             c->sc.direct.mi = mi, c->sc.direct.root = ref->second.root4, c->sc.direct.on = 1u;
-            c->direct_scene = true;
+            c->trace.direct_scene = true;
         }
     }
     // ray-sort grid: true bounds of the TLAS root (Scene::GetBounds takes fminf for the max corner, SceneCPU.cpp:1553)
@@ -503,7 +503,7 @@ static int upload_bottom_level(rayhip_ctx *c, const rayhip_scene_desc *d, rayhip
     }
     HIP_TRY(hipStreamSynchronize(c->stream)); // the builders' arrays go out of scope
     // "small": the BLAS working set (nodes + triangle records) fits one XCD's 4 MB L2 with room to spare
-    c->small_scene = wide != 0 && getenv("RAYHIP_NO_SMALL") == nullptr && wide_bytes + n_tris * sizeof(rayhip_tri_accel) <= (size_t(2) << 20);
+    c->trace.small_scene = wide != 0 && getenv("RAYHIP_NO_SMALL") == nullptr && wide_bytes + n_tris * sizeof(rayhip_tri_accel) <= (size_t(2) << 20);
     // the meshes in use, for rayhip_scene_update_instances: the roots of their trees as uploaded
     rayhip_update::collect_mesh_refs(n2, n2_count, mis, d->mesh_instances_count, tlas_root, wide ? blas_root4.data() : nullptr, c->mesh_refs);
     // ... and for rayhip_scene_update_vertices: the bottom-level nodes by height, the live instances (refit.h)
@@ -632,15 +632,27 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
     return 0;
 }
 
-int rayhip_direct_entry(rayhip_ctx *c) { return c && c->have_scene && c->direct() && (c->refill_waves || c->shadow_refill) ? 1 : 0; }
+// the reports ask the function the launches ask (trace_select.h), for calls without flags
+int rayhip_direct_entry(rayhip_ctx *c) {
+    if (!c || !c->have_scene) {
+        return 0;
+    }
+    const bool d = c->direct();
+    const bool any = is_direct(closest_form(c->trace, c->wide, d, TraceRole::Primary, 0u)) ||
+                     is_direct(closest_form(c->trace, c->wide, d, TraceRole::Secondary, 0u)) ||
+                     is_direct(shadow_form(c->trace, c->wide, d, TraceRole::Secondary, 0u, false));
+    return any ? 1 : 0;
+}
 
 int rayhip_scene_bvh_width(rayhip_ctx *c) { return !c || !c->have_scene ? 0 : c->wide ? c->wide : 2; }
 
+// the kernel of the secondary bounces: 2 = pooled, 1 = a refill form, 0 = plain (or no scene)
 int rayhip_closest_hit_form(rayhip_ctx *c) {
-    if (!c || !c->have_scene || !c->wide || !c->refill_waves) {
+    if (!c || !c->have_scene) {
         return 0;
     }
-    return (c->wide == 4 && c->refill_pool && c->pool_scene) ? 2 : 1;
+    const ClosestForm f = closest_form(c->trace, c->wide, c->direct(), TraceRole::Secondary, 0u);
+    return f == ClosestForm::Pooled ? 2 : (is_lane(f) || is_whole(f)) ? 1 : 0;
 }
 
 // ---- instance / light / environment update without a new upload of the geometry -----------------------------------------
