@@ -461,6 +461,46 @@ RAYHIP_API int rayhip_skin_create(rayhip_ctx *ctx, const rayhip_skin_desc *desc,
 RAYHIP_API int rayhip_skin_destroy(rayhip_ctx *ctx, int skin);
 RAYHIP_API int rayhip_scene_pose_skins(rayhip_ctx *ctx, int n, const int *skins, const float *const *palettes); /* palettes[i]: bones_count x 12 */
 
+/* MORPH TARGETS (blend shapes, shape keys), alone or ahead of a skin (ray_amd/csrc/morph.h, morph.hip.h).  A morph set keeps the
+ * base records of a vertex range and the deltas of its targets on the device; a pose is one float weight per target -- any finite
+ * value, negative ones and ones above 1 included.  Targets are sparse: each names the vertices it moves (indices relative to the
+ * set's first vertex, strictly ascending) with a position delta and, optionally, normal and bitangent deltas.  The posed record is
+ * the base record plus, target after target in ascending order, weight * delta (targets of weight 0 are skipped); normals and
+ * bitangents are normalised afterwards, uvs copied; a vertex that no target with a weight moves keeps its base record bytewise.
+ * MORPH, THEN SKIN: for a vertex that lies in a morph set and in a skin, the skin poses the morphed record in place of its own rest
+ * record.  A set lies inside ONE live skin or in none; a skin may hold any number of disjoint sets.
+ * rayhip_scene_pose poses the named sets (weights[i]: the targets_count floats of morphs[i]) and the named skins (palettes[i] belongs
+ * to skins[i]) into a staging array and refits ONCE, as rayhip_scene_pose_skins does; like it, it is stateless: a pose starts from
+ * the base and rest records, nothing accumulates.  A set inside a live skin and that skin are posed TOGETHER: naming one of them
+ * without the other is refused -- also by rayhip_scene_pose_skins, which refuses a skin that holds a live set.
+ * Up to 16 sets are live per context, over disjoint ranges; overlap with a skin is not looked at when either is created.  Every
+ * rayhip_scene_upload[_blob] discards them all.  *out_morph is a handle of 16 or more -- never one of the return codes -- and the
+ * handle of a destroyed or discarded set names no later one.
+ * Return values as for the skins.  2 = needs rayhip_scene_upload, nothing touched: no scene, a handle that is not live, the 8-wide
+ * tree, a tree of more than 128 levels, or (at create time) a range that holds a vertex of a triangle light while
+ * rayhip_scene_refit_lights is off.
+ * 1 = error.  rayhip_morph_create: a null pointer, count == 0 or a range outside the array or overlapping a live set, a
+ * seventeenth set, targets_count outside 1..65536, indices of a target that are not strictly ascending or >= count, a delta that is
+ * not finite, more than 2^32 - 1 entries in total.  rayhip_scene_pose: bad counts or null arrays, a handle named twice, a weight that
+ * is not finite, a named set that straddles the boundary of a live skin, a set and the skin around it not named together, or a posed
+ * position of a vertex in use that is not finite -- all found before the vertex array is written. */
+typedef struct rayhip_morph_target {
+    uint32_t count;             /* vertices this target moves; 0 is allowed */
+    const uint32_t *vertices;   /* count indices RELATIVE to the set's first_vertex, strictly ascending */
+    const float *dp;            /* count x 3 */
+    const float *dn, *db;       /* count x 3 each; NULL = no normal / bitangent deltas (zeros) */
+} rayhip_morph_target;
+typedef struct rayhip_morph_desc {
+    uint32_t first_vertex, count;      /* range of the uploaded vertex array this set drives */
+    const rayhip_vertex *base;         /* count records; NULL = what the device holds for the range now */
+    uint32_t targets_count;            /* 1 .. 65536 */
+    const rayhip_morph_target *targets;
+} rayhip_morph_desc;
+RAYHIP_API int rayhip_morph_create(rayhip_ctx *ctx, const rayhip_morph_desc *desc, int *out_morph);
+RAYHIP_API int rayhip_morph_destroy(rayhip_ctx *ctx, int morph);
+RAYHIP_API int rayhip_scene_pose(rayhip_ctx *ctx, int n_morphs, const int *morphs, const float *const *weights, /* weights[i]: targets_count floats */
+                                 int n_skins, const int *skins, const float *const *palettes);
+
 /* Emissive meshes that deform: 0 = off (default): unchanged behaviour.  1 = vertex updates and poses may move triangle lights.
  * With the switch on, rayhip_scene_update_vertices[_blob|_device] accept changed vertices of triangle lights, rayhip_skin_create accepts
  * ranges that hold such vertices, and every vertex update or pose refits ON THE DEVICE, behind the geometry and before it returns
@@ -475,8 +515,8 @@ RAYHIP_API int rayhip_scene_pose_skins(rayhip_ctx *ctx, int n, const int *skins,
  * The switch is a property of the context and survives uploads; it may be set before or after rayhip_scene_upload[_blob] -- whichever
  * comes second prepares what the refit needs.  rayhip_scene_update_instances behaves as ever: the host's lights, light tree and
  * vertices' kept copies replace the device's, and the host's tree describes the HOST's vertices -- a caller who deforms on the device
- * poses or updates again after an instance update.  Returns 0; 1 = error, among them turning the switch off while a live skin covers
- * a vertex of a triangle light (destroy the skin first).  After it is turned off, "changed" is judged against the vertices the
+ * poses or updates again after an instance update.  Returns 0; 1 = error, among them turning the switch off while a live skin or morph set
+ * covers a vertex of a triangle light (destroy it first).  After it is turned off, "changed" is judged against the vertices the
  * lights on the device describe at that moment. */
 RAYHIP_API int rayhip_scene_refit_lights(rayhip_ctx *ctx, int on);
 

@@ -31,6 +31,7 @@
 #include "lbvh.hip.h"
 #include "refit.hip.h"
 #include "skin.hip.h"
+#include "morph.hip.h"
 #include "light_refit.hip.h"
 #include "scene_blob.h"
 #include "scene_rebuild.h"

@@ -199,8 +199,28 @@ struct rayhip_ctx {
             k.rest.release(), k.indices.release(), k.weights.release();
         }
     }
-    DevBuf skin_stage;    // the posed vertices of one rayhip_scene_pose_skins call, skin after skin (sized to the largest call seen)
-    DevBuf skin_palettes; // ... and its palettes
+    // morph sets (rayhip_morph_create, morph.h): base records and the row table of the targets' deltas of a vertex range, on the device
+    // until the next scene upload
+    struct Morph {
+        bool live = false;
+        int id = 0; // the handle the caller holds, made as a skin's
+        uint32_t first = 0, count = 0, targets_count = 0;
+        DevBuf base, row, entries; // rayhip_vertex [count], uint32 [count + 1], rayhip_morph::Entry [row[count]]
+    } morphs[rayhip_morph::MAX_MORPHS];
+    uint32_t morph_serial = 0;
+    // the live morph set handle `id` names, or null
+    Morph *morph_of(const int id) {
+        Morph &m = morphs[id & int(rayhip_morph::MAX_MORPHS - 1)];
+        return id > 0 && m.live && m.id == id ? &m : nullptr;
+    }
+    void discard_morphs() {
+        for (Morph &m : morphs) {
+            m.live = false;
+            m.base.release(), m.row.release(), m.entries.release();
+        }
+    }
+    DevBuf skin_stage;    // the posed vertices of one rayhip_scene_pose[_skins] call, range after range (sized to the largest call seen)
+    DevBuf skin_palettes; // ... and its palettes and morph weights
     DevBuf skin_counters; // [0] used vertices without a finite position, [1] changed light vertices
     // ---- (deforming: end) ----
     bool adaptive_dirty = false; // a pass ran with variance_threshold != 0 since the last Clear / Resize: required_samples may
@@ -879,6 +899,7 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
     }
     c->stack_spill2.release();
     c->discard_skins();
+    c->discard_morphs();
     for (DevBuf *b : {&c->refit.level_nodes, &c->refit.first_entry, &c->refit.scratch, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices,
                       &c->light_refit.level_nodes, &c->light_refit.leaf, &c->light_refit.node_summary, &c->light_refit.slot_scale, &c->skin_stage,
                       &c->skin_palettes, &c->skin_counters}) {

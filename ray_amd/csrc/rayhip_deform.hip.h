@@ -2,7 +2,8 @@
 // deforming a scene that is on the device.  In reading order: the tables an upload or instance update leaves behind (prepare_refit,
 // keep_light_vertices, upload_vertex_checks, prepare_light_refit), the phase stamps, the preconditions, the light refit and the
 // geometry refit behind new vertices, the entry points (rayhip_scene_update_vertices, its _blob and _device forms; refit.h), the
-// skins (rayhip_skin_create / _destroy, rayhip_scene_pose_skins; skin.h) and the switch (rayhip_scene_refit_lights; light_refit.h).
+// skins (rayhip_skin_create / _destroy, rayhip_scene_pose_skins; skin.h), the morph sets (rayhip_morph_create / _destroy,
+// rayhip_scene_pose; morph.h) and the switch (rayhip_scene_refit_lights; light_refit.h).
 #pragma once
 
 // what the refit needs of the upload's half of the launcher (rayhip_upload.hip.h)
@@ -508,6 +509,57 @@ int rayhip_skin_destroy(rayhip_ctx *c, int skin) {
     return 0;
 }
 
+// ---- what the two pose calls share (rayhip_scene_pose_skins, rayhip_scene_pose): the staging array, the counter, the copies, the refit ----
+// vertices [first, first + count) of the scene, posed into the staging array from record `at` on
+struct StagedRange {
+    uint32_t first, count;
+    size_t at;
+};
+
+// waits for pending passes, stamps "begin", and makes room: `stage_vertices` staged records, `floats` of palettes and weights, the counters (zeroed)
+static int pose_begin(rayhip_ctx *c, const VertexStamps &st, const size_t stage_vertices, const size_t floats) {
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    if (c->skin_stage.alloc(stage_vertices * sizeof(rayhip_vertex)) || c->skin_palettes.alloc(floats * sizeof(float)) || c->skin_counters.alloc(2 * sizeof(uint32_t))) {
+        return 1;
+    }
+    HIP_TRY(hipMemsetAsync(c->skin_counters.as<uint32_t>(), 0, 2 * sizeof(uint32_t), c->stream));
+    return 0;
+}
+
+// k_skin_vertices over vertices [off, off + count) of skin `k` (its pointers offset: 8-byte index records and 16-byte weight records stay
+// aligned at any vertex), posed into the staging array where the skin's range begins at record `at`
+static int launch_skin_segment(rayhip_ctx *c, const rayhip_ctx::Skin &k, const uint32_t off, const uint32_t count, const float *d_palette, const size_t at) {
+    if (count == 0) {
+        return 0;
+    }
+    rayhip_skin::k_skin_vertices<<<(count + 255) / 256, 256, 0, c->stream>>>(k.rest.as<rayhip_vertex>() + off, k.indices.as<uint16_t>() + size_t(off) * 4,
+                                                                            k.weights.as<float>() + size_t(off) * 4, count, d_palette, k.bones_count,
+                                                                            c->refit.d_vertex_used.as<uint8_t>() + k.first + off,
+                                                                            c->skin_stage.as<rayhip_vertex>() + at + off, c->skin_counters.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// behind the launches: the counter comes back; where it is zero the staged ranges are copied into the vertex array and ONE refit follows
+static int pose_commit(rayhip_ctx *c, const VertexStamps &st, const std::vector<StagedRange> &staged) {
+    hipStream_t s = c->stream;
+    uint32_t counters[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counters, c->skin_counters.as<uint32_t>(), sizeof(counters), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (the caller's palettes and weights may go away after this)
+    HIP_TRY(st.stamp("vertices posed"));
+    if (counters[0] != 0) {
+        return fail("%s: the posed position of %u vertices is not finite", st.who, counters[0]);
+    }
+    // (the counter is back and zero: from here on the live vertex array is written)
+    for (const StagedRange &r : staged) {
+        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + r.first, c->skin_stage.as<rayhip_vertex>() + r.at, size_t(r.count) * sizeof(rayhip_vertex),
+                               hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(st.stamp("vertices copied"));
+    return refit_after_vertices(c, st);
+}
+
 int rayhip_scene_pose_skins(rayhip_ctx *c, int n, const int *skins, const float *const *palettes) {
     if (!c || use_device(c)) {
         return 1;
@@ -534,51 +586,253 @@ int rayhip_scene_pose_skins(rayhip_ctx *c, int n, const int *skins, const float 
         }
         stage_vertices += c->skin_of(skins[i])->count, palette_floats += size_t(c->skin_of(skins[i])->bones_count) * 12;
     }
+    for (int i = 0; i < n; ++i) { // (cannot occur without a live morph set)
+        const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
+        for (const rayhip_ctx::Morph &m : c->morphs) {
+            if (m.live && m.first < k.first + k.count && k.first < m.first + m.count) {
+                return fail("rayhip_scene_pose_skins: skin %d holds morph set %d; pose them together (rayhip_scene_pose)", k.id, m.id);
+            }
+        }
+    }
     if (n == 0) {
         return 0;
     }
     const VertexStamps st{c, "rayhip_scene_pose_skins"};
-    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
-    HIP_TRY(st.stamp("begin"));
-    hipStream_t s = c->stream;
-    if (c->skin_stage.alloc(stage_vertices * sizeof(rayhip_vertex)) || c->skin_palettes.alloc(palette_floats * sizeof(float)) ||
-        c->skin_counters.alloc(2 * sizeof(uint32_t))) {
+    if (pose_begin(c, st, stage_vertices, palette_floats)) {
         return 1;
     }
-    uint32_t *d_counters = c->skin_counters.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
+    std::vector<StagedRange> staged;
     {
         size_t at_vertex = 0, at_float = 0;
         for (int i = 0; i < n; ++i) {
             const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
             float *d_palette = c->skin_palettes.as<float>() + at_float;
-            HIP_TRY(hipMemcpyAsync(d_palette, palettes[i], size_t(k.bones_count) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
-            rayhip_skin::k_skin_vertices<<<(k.count + 255) / 256, 256, 0, s>>>(k.rest.as<rayhip_vertex>(), k.indices.as<uint16_t>(), k.weights.as<float>(), k.count,
-                                                                              d_palette, k.bones_count, c->refit.d_vertex_used.as<uint8_t>() + k.first,
-                                                                              c->skin_stage.as<rayhip_vertex>() + at_vertex, d_counters);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(d_palette, palettes[i], size_t(k.bones_count) * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+            if (launch_skin_segment(c, k, 0, k.count, d_palette, at_vertex)) {
+                return 1;
+            }
+            staged.push_back({k.first, k.count, at_vertex});
             at_vertex += k.count, at_float += size_t(k.bones_count) * 12;
         }
     }
-    uint32_t counters[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s)); // (the caller's palettes may go away after this)
-    HIP_TRY(st.stamp("vertices posed"));
-    if (counters[0] != 0) {
-        return fail("rayhip_scene_pose_skins: the posed position of %u vertices is not finite", counters[0]);
+    return pose_commit(c, st, staged);
+}
+
+// ---- morph sets (morph.h, morph.hip.h) ------------------------------------------------------------------------------------------------------
+int rayhip_morph_create(rayhip_ctx *c, const rayhip_morph_desc *d, int *out_morph) {
+    if (!c || use_device(c)) {
+        return 1;
     }
-    // (the counter is back and zero: from here on the live vertex array is written)
-    {
-        size_t at_vertex = 0;
-        for (int i = 0; i < n; ++i) {
-            const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
-            HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + k.first, c->skin_stage.as<rayhip_vertex>() + at_vertex, size_t(k.count) * sizeof(rayhip_vertex),
-                                   hipMemcpyDeviceToDevice, s));
-            at_vertex += k.count;
+    if (!d || !out_morph || !d->targets) {
+        return fail("rayhip_morph_create: a null pointer");
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_morph_create")) {
+        return rc;
+    }
+    if (d->count == 0 || uint64_t(d->first_vertex) + d->count > c->geometry.vertices) {
+        return outside_the_scene(c, "rayhip_morph_create", d->first_vertex, d->count);
+    }
+    if (d->targets_count == 0 || d->targets_count > rayhip_morph::MAX_TARGETS) {
+        return fail("rayhip_morph_create: %u targets (1 .. %u)", d->targets_count, rayhip_morph::MAX_TARGETS);
+    }
+    int slot = -1;
+    for (int k = int(rayhip_morph::MAX_MORPHS) - 1; k >= 0; --k) {
+        const rayhip_ctx::Morph &o = c->morphs[k];
+        if (!o.live) {
+            slot = k;
+        } else if (d->first_vertex < o.first + o.count && o.first < d->first_vertex + d->count) {
+            return fail("rayhip_morph_create: vertices [%u, %u + %u) overlap morph set %d", d->first_vertex, d->first_vertex, d->count, o.id);
         }
     }
-    HIP_TRY(st.stamp("vertices copied"));
-    return refit_after_vertices(c, st);
+    if (slot < 0) {
+        return fail("rayhip_morph_create: %u morph sets are live already", rayhip_morph::MAX_MORPHS);
+    }
+    {
+        uint32_t where = 0;
+        if (const int bad = rayhip_morph::validate_targets(d->targets, d->targets_count, d->count, where)) {
+            return bad == 1   ? fail("rayhip_morph_create: a null pointer in target %u", where)
+                   : bad == 2 ? fail("rayhip_morph_create: the vertices of target %u are not strictly ascending below %u", where, d->count)
+                   : bad == 3 ? fail("rayhip_morph_create: a delta of target %u is not finite", where)
+                              : fail("rayhip_morph_create: more than 2^32 - 1 entries in all");
+        }
+    }
+    if (const uint32_t *pinned = pinned_light_vertex(c, d->first_vertex, d->count, nullptr)) { // (a pose may put it anywhere)
+        (void)fail("rayhip_morph_create: vertex %u belongs to a triangle light; lights are not rebuilt by a pose", *pinned);
+        return 2;
+    }
+    std::vector<uint32_t> row;
+    std::vector<rayhip_morph::Entry> entries;
+    rayhip_morph::build_rows(d->targets, d->targets_count, d->count, row, entries);
+    rayhip_ctx::Morph &m = c->morphs[slot];
+    const size_t n = d->count;
+    if (m.base.alloc(n * sizeof(rayhip_vertex)) || upload(c, m.row, row.data(), row.size() * sizeof(uint32_t)) ||
+        upload(c, m.entries, entries.data(), entries.size() * sizeof(rayhip_morph::Entry))) {
+        return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(m.base.p, d->base ? static_cast<const void *>(d->base) : static_cast<const void *>(c->vertices.as<rayhip_vertex>() + d->first_vertex),
+                           n * sizeof(rayhip_vertex), d->base ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the table and the caller's arrays may go away after this call
+    c->morph_serial = (c->morph_serial % 0x7ffffffu) + 1; // (as a skin's handle)
+    m.live = true, m.id = int(c->morph_serial << 4) | slot, m.first = d->first_vertex, m.count = d->count, m.targets_count = d->targets_count;
+    *out_morph = m.id;
+    return 0;
+}
+
+int rayhip_morph_destroy(rayhip_ctx *c, int morph) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (!c->morph_of(morph)) {
+        (void)fail("rayhip_morph_destroy: morph set %d is not live", morph);
+        return 2;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rayhip_ctx::Morph &m = *c->morph_of(morph);
+    m.live = false;
+    m.base.release(), m.row.release(), m.entries.release();
+    return 0;
+}
+
+// Morph sets and skins in one pose.  A skin's range is staged as a sequence of launches over segments -- [plain][set A][plain][set B]... --
+// plain ones by k_skin_vertices with its pointers offset, covered ones by the fused kernel: no kernel looks for the set it is in.
+int rayhip_scene_pose(rayhip_ctx *c, int n_morphs, const int *morphs, const float *const *weights, int n_skins, const int *skins, const float *const *palettes) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (n_morphs < 0 || n_morphs > int(rayhip_morph::MAX_MORPHS) || n_skins < 0 || n_skins > int(rayhip_skin::MAX_SKINS) ||
+        (n_morphs > 0 && (!morphs || !weights)) || (n_skins > 0 && (!skins || !palettes))) {
+        return fail("rayhip_scene_pose: bad arguments");
+    }
+    if (n_morphs == 0 && n_skins == 0) {
+        return 0;
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_scene_pose")) {
+        return rc;
+    }
+    size_t stage_vertices = 0, floats = 0;
+    for (int i = 0; i < n_morphs; ++i) {
+        const rayhip_ctx::Morph *m = c->morph_of(morphs[i]);
+        if (!m) {
+            (void)fail("rayhip_scene_pose: morph set %d is not live", morphs[i]);
+            return 2;
+        }
+        if (!weights[i]) {
+            return fail("rayhip_scene_pose: no weights for morph set %d", morphs[i]);
+        }
+        for (int j = 0; j < i; ++j) {
+            if (morphs[j] == morphs[i]) {
+                return fail("rayhip_scene_pose: morph set %d is named twice", morphs[i]);
+            }
+        }
+        for (uint32_t t = 0; t < m->targets_count; ++t) {
+            if (!rayhip_skin::finite_f(weights[i][t])) {
+                return fail("rayhip_scene_pose: the weight of target %u of morph set %d is not finite", t, morphs[i]);
+            }
+        }
+        floats += m->targets_count;
+    }
+    for (int i = 0; i < n_skins; ++i) {
+        if (!c->skin_of(skins[i])) {
+            (void)fail("rayhip_scene_pose: skin %d is not live", skins[i]);
+            return 2;
+        }
+        if (!palettes[i]) {
+            return fail("rayhip_scene_pose: no palette for skin %d", skins[i]);
+        }
+        for (int j = 0; j < i; ++j) {
+            if (skins[j] == skins[i]) {
+                return fail("rayhip_scene_pose: skin %d is named twice", skins[i]);
+            }
+        }
+        stage_vertices += c->skin_of(skins[i])->count, floats += size_t(c->skin_of(skins[i])->bones_count) * 12;
+    }
+    const auto named = [](const int *ids, const int n, const int id) { return std::find(ids, ids + n, id) != ids + n; };
+    const auto overlap = [](const rayhip_ctx::Morph &m, const rayhip_ctx::Skin &k) { return m.first < k.first + k.count && k.first < m.first + m.count; };
+    std::vector<bool> in_a_skin(size_t(n_morphs), false);
+    for (int i = 0; i < n_morphs; ++i) {
+        const rayhip_ctx::Morph &m = *c->morph_of(morphs[i]);
+        for (const rayhip_ctx::Skin &k : c->skins) {
+            if (!k.live || !overlap(m, k)) {
+                continue;
+            }
+            if (m.first < k.first || m.first + m.count > k.first + k.count) {
+                return fail("rayhip_scene_pose: morph set %d straddles the boundary of skin %d", m.id, k.id);
+            }
+            if (!named(skins, n_skins, k.id)) {
+                return fail("rayhip_scene_pose: morph set %d lies inside skin %d; pose them together", m.id, k.id);
+            }
+            in_a_skin[size_t(i)] = true;
+        }
+        stage_vertices += in_a_skin[size_t(i)] ? 0 : m.count;
+    }
+    for (int i = 0; i < n_skins; ++i) {
+        const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
+        for (const rayhip_ctx::Morph &m : c->morphs) {
+            if (m.live && overlap(m, k) && !named(morphs, n_morphs, m.id)) {
+                return fail("rayhip_scene_pose: skin %d holds morph set %d; pose them together", k.id, m.id);
+            }
+        }
+    }
+    const VertexStamps st{c, "rayhip_scene_pose"};
+    if (pose_begin(c, st, stage_vertices, floats)) {
+        return 1;
+    }
+    hipStream_t s = c->stream;
+    uint32_t *d_counters = c->skin_counters.as<uint32_t>();
+    const uint8_t *d_used = c->refit.d_vertex_used.as<uint8_t>();
+    std::vector<StagedRange> staged;
+    size_t at_vertex = 0, at_float = 0;
+    std::vector<const float *> d_weights(size_t(n_morphs), nullptr);
+    for (int i = 0; i < n_morphs; ++i) {
+        const rayhip_ctx::Morph &m = *c->morph_of(morphs[i]);
+        float *d_w = c->skin_palettes.as<float>() + at_float;
+        HIP_TRY(hipMemcpyAsync(d_w, weights[i], size_t(m.targets_count) * sizeof(float), hipMemcpyHostToDevice, s));
+        d_weights[size_t(i)] = d_w, at_float += m.targets_count;
+    }
+    for (int i = 0; i < n_skins; ++i) {
+        const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
+        float *d_palette = c->skin_palettes.as<float>() + at_float;
+        HIP_TRY(hipMemcpyAsync(d_palette, palettes[i], size_t(k.bones_count) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+        std::vector<int> inside; // the named sets this skin holds, by first vertex
+        for (int j = 0; j < n_morphs; ++j) {
+            if (overlap(*c->morph_of(morphs[j]), k)) {
+                inside.push_back(j);
+            }
+        }
+        std::sort(inside.begin(), inside.end(), [&](const int x, const int y) { return c->morph_of(morphs[x])->first < c->morph_of(morphs[y])->first; });
+        uint32_t at = 0; // vertices of the skin staged so far
+        for (const int j : inside) {
+            const rayhip_ctx::Morph &m = *c->morph_of(morphs[j]);
+            const uint32_t off = m.first - k.first;
+            if (launch_skin_segment(c, k, at, off - at, d_palette, at_vertex)) {
+                return 1;
+            }
+            rayhip_morph::k_morph_skin_vertices<<<(m.count + 255) / 256, 256, 0, s>>>(
+                m.base.as<rayhip_vertex>(), m.row.as<uint32_t>(), m.entries.as<rayhip_morph::Entry>(), m.count, d_weights[size_t(j)], m.targets_count,
+                k.indices.as<uint16_t>() + size_t(off) * 4, k.weights.as<float>() + size_t(off) * 4, d_palette, k.bones_count, d_used + m.first,
+                c->skin_stage.as<rayhip_vertex>() + at_vertex + off, d_counters);
+            HIP_TRY(hipGetLastError());
+            at = off + m.count;
+        }
+        if (launch_skin_segment(c, k, at, k.count - at, d_palette, at_vertex)) {
+            return 1;
+        }
+        staged.push_back({k.first, k.count, at_vertex});
+        at_vertex += k.count, at_float += size_t(k.bones_count) * 12;
+    }
+    for (int i = 0; i < n_morphs; ++i) {
+        if (in_a_skin[size_t(i)]) {
+            continue;
+        }
+        const rayhip_ctx::Morph &m = *c->morph_of(morphs[i]);
+        rayhip_morph::k_morph_vertices<<<(m.count + 255) / 256, 256, 0, s>>>(m.base.as<rayhip_vertex>(), m.row.as<uint32_t>(), m.entries.as<rayhip_morph::Entry>(),
+                                                                             m.count, d_weights[size_t(i)], m.targets_count, d_used + m.first,
+                                                                             c->skin_stage.as<rayhip_vertex>() + at_vertex, d_counters);
+        HIP_TRY(hipGetLastError());
+        staged.push_back({m.first, m.count, at_vertex});
+        at_vertex += m.count;
+    }
+    return pose_commit(c, st, staged);
 }
 
 // ---- the switch: vertex updates and poses may move triangle lights (light_refit.h) --------------------------------------------------
@@ -597,6 +851,13 @@ int rayhip_scene_refit_lights(rayhip_ctx *c, int on) {
             for (const auto &kept : c->refit.light_vertices) {
                 if (k.live && kept.first >= k.first && kept.first - k.first < k.count) {
                     return fail("rayhip_scene_refit_lights: skin %d covers vertex %u of a triangle light; destroy it first", k.id, kept.first);
+                }
+            }
+        }
+        for (const rayhip_ctx::Morph &m : c->morphs) {
+            for (const auto &kept : c->refit.light_vertices) {
+                if (m.live && kept.first >= m.first && kept.first - m.first < m.count) {
+                    return fail("rayhip_scene_refit_lights: morph set %d covers vertex %u of a triangle light; destroy it first", m.id, kept.first);
                 }
             }
         }

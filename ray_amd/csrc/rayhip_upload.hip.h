@@ -2,7 +2,7 @@
 // getting a scene onto the device: the sky, lights and their derived tables, the scene view, the top level rebuilt on the device,
 // rayhip_scene_upload (validation, then its phases: leaf refinement, layout, bottom level and wide collapse, shading arrays, lights,
 // textures), rayhip_scene_update_instances, filter table, tonemap LUT, the blob forms, the hook rayhip_k_read_accel.  What deforms a
-// scene that is there (vertex updates, skins, the light refit) and the tables an upload leaves for it: rayhip_deform.hip.h.
+// scene that is there (vertex updates, skins, morph sets, the light refit) and the tables an upload leaves for it: rayhip_deform.hip.h.
 #pragma once
 
 // the physical sky (rayhip_sky + its tables and textures: 1.6 MB): device copies and the view the kernels read; the directional-light
@@ -566,6 +566,7 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
     const UploadTrace trace;
     trace("begin");
     c->discard_skins(); // (a skin names a range of the vertex array this call replaces)
+    c->discard_morphs(); // (... and so does a morph set)
     const rayhip_layout::AlignedDesc aligned(*d_in); // see bvh_layout.h
     const rayhip_scene_desc *d = &aligned.d;
     if (d->env.qtree_levels < 0 || d->env.qtree_levels > 16) {

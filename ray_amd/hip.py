@@ -80,6 +80,15 @@ class SkinDesc(C.Structure):  # rayhip_skin_desc
                 ("bones_count", C.c_uint32)]
 
 
+class MorphTarget(C.Structure):  # rayhip_morph_target
+    _fields_ = [("count", C.c_uint32), ("vertices", C.c_void_p), ("dp", C.c_void_p), ("dn", C.c_void_p), ("db", C.c_void_p)]
+
+
+class MorphDesc(C.Structure):  # rayhip_morph_desc
+    _fields_ = [("first_vertex", C.c_uint32), ("count", C.c_uint32), ("base", C.c_void_p), ("targets_count", C.c_uint32),
+                ("targets", C.POINTER(MorphTarget))]
+
+
 CACHE_ENTRIES = 1 << 22  # slots of the spatial cache's key table (rt_cache.h)
 # rayhip_cache_vertex: one vertex of a cache-update bounce
 CACHE_VERTEX_DTYPE = np.dtype([("o", "<f4", 3), ("t", "<f4"), ("d", "<f4", 3), ("path", "<u4"), ("n", "<f4", 3), ("ends", "<u4"),
@@ -102,7 +111,7 @@ assert LIGHT_NODE_DTYPE.itemsize == 208
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "scene_refit_lights", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "scene_refit_lights", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
@@ -207,6 +216,9 @@ class Library:
             f("skin_create").argtypes = [vp, C.POINTER(SkinDesc), C.POINTER(C.c_int)]
             f("skin_destroy").argtypes = [vp, C.c_int]
             f("scene_pose_skins").argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
+            f("morph_create").argtypes = [vp, C.POINTER(MorphDesc), C.POINTER(C.c_int)]
+            f("morph_destroy").argtypes = [vp, C.c_int]
+            f("scene_pose").argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(vp), C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
             f("scene_refit_lights").argtypes = [vp, C.c_int]
 
     def fn(self, name):
@@ -368,6 +380,59 @@ class Context:
         c_ids = (C.c_int * max(len(ids), 1))(*ids)
         c_ptrs = (C.c_void_p * max(len(ids), 1))(*[a.ctypes.data for a in arrays])
         rc = self.L.fn("scene_pose_skins")(self._ctx, len(ids), c_ids, c_ptrs)
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def create_morph(self, first: int, count: int, base, targets) -> int:
+        """a morph set over vertices [first, first + count) (rayhip_morph_create): `base` VERTEX_DTYPE records or None (what the device
+        holds for the range now), `targets` a list of (vertices, dp, dn or None, db or None) -- indices relative to `first`, strictly
+        ascending, and [n][3] float32 deltas.  Returns the set's id (16 or more), or 2 where the ABI returns 2; an error raises."""
+        if base is not None:
+            base = np.ascontiguousarray(base)
+            assert base.dtype == VERTEX_DTYPE and len(base) == count
+        keep = []  # the arrays the description points into
+
+        def ptr(a, dtype, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype).reshape(shape)
+            keep.append(a)
+            return a.ctypes.data
+
+        c_targets = (MorphTarget * max(len(targets), 1))()
+        for k, (vertices, dp, dn, db) in enumerate(targets):
+            n = len(vertices)
+            c_targets[k] = MorphTarget(n, ptr(vertices, np.uint32, (n,)), ptr(dp, np.float32, (n, 3)), ptr(dn, np.float32, (n, 3)),
+                                       ptr(db, np.float32, (n, 3)))
+        d = MorphDesc(int(first), int(count), base.ctypes.data if base is not None else None, len(targets), c_targets)
+        out = C.c_int(-1)
+        rc = self.L.fn("morph_create")(self._ctx, C.byref(d), C.byref(out))
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return int(out.value)
+
+    def destroy_morph(self, morph: int) -> int:
+        rc = self.L.fn("morph_destroy")(self._ctx, int(morph))
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def pose(self, morph_weights: dict, palettes: dict) -> int:
+        """{morph set id: weights [targets] float32} and {skin id: palette [bones][3][4] float32}: every named set and skin posed from its
+        base / rest records -- morph, then skin, where a skin holds a set -- and ONE refit (rayhip_scene_pose); returns as pose_skins()"""
+        m_ids, k_ids = list(morph_weights), list(palettes)
+        w = [np.ascontiguousarray(morph_weights[k], dtype=np.float32).ravel() for k in m_ids]
+        p = [np.ascontiguousarray(palettes[k], dtype=np.float32) for k in k_ids]
+        assert all(a.ndim == 3 and a.shape[1:] == (3, 4) for a in p)
+        c_m = (C.c_int * max(len(m_ids), 1))(*m_ids)
+        c_w = (C.c_void_p * max(len(m_ids), 1))(*[a.ctypes.data for a in w])
+        c_k = (C.c_int * max(len(k_ids), 1))(*k_ids)
+        c_p = (C.c_void_p * max(len(k_ids), 1))(*[a.ctypes.data for a in p])
+        rc = self.L.fn("scene_pose")(self._ctx, len(m_ids), c_m, c_w, len(k_ids), c_k, c_p)
         if rc == 2:
             return 2
         self.L.check(rc)
