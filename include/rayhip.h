@@ -501,6 +501,39 @@ RAYHIP_API int rayhip_morph_destroy(rayhip_ctx *ctx, int morph);
 RAYHIP_API int rayhip_scene_pose(rayhip_ctx *ctx, int n_morphs, const int *morphs, const float *const *weights, /* weights[i]: targets_count floats */
                                  int n_skins, const int *skins, const float *const *palettes);
 
+/* NORMAL SETS: shading normals and bitangents derived on the device from the positions that are in the vertex array
+ * (ray_amd/csrc/normals.h, normals.hip.h) -- for a caller that has positions only (a cloth or wave simulation, its own kernels), for
+ * morph targets without normal deltas, for skins under shear.  While a set is live, EVERY call that writes the vertex array --
+ * rayhip_scene_update_vertices[_blob|_device], rayhip_scene_pose_skins, rayhip_scene_pose -- recomputes, behind its checks and its copy
+ * and ahead of the refit, the normals and / or bitangents of the set's range IN PLACE: every live set, whatever range the call wrote.
+ * Positions and uvs are only read; with no live set every call does what it did.  Overlap with skins and morph sets is the point.
+ * Faces: the triangles the bottom-level trees reach that have a corner in the range, in ascending triangle number; a triangle that had
+ * no area AT UPLOAD is in no tree and never contributes, whatever its corners become.  Corners outside the range are read as they are.
+ * Normal: the sum of the unnormalised face normals cross(p1 - p0, p2 - p0) (area weights) over the corners of every vertex of the
+ * vertex's weld group, normalised; a sum without length keeps the normal the record arrived with.  Bitangent: as the reference's scene
+ * build derives it from the uvs (ComputeTangentBasis) -- the sum T of the face tangents over the vertex's OWN corners (never welded: uv
+ * seams differ), then cross(n, T) normalised, n being the new normal where the set recomputes it; at the upload pose a set with
+ * RAYHIP_NORMALS_B alone reproduces the stored bitangents of a mesh the scene build derived them for, bit for bit.  A vertex of the
+ * range without a reachable triangle keeps its record bytewise.
+ * `weld`: the scene build splits a vertex where tangents disagree and appends twins; weld[i] names the canonical vertex of i's
+ * smoothing group so that twins (or any vertices the caller calls one) share a normal.
+ * Up to 16 sets are live per context, over disjoint ranges; rayhip_scene_upload[_blob] discards them all, rayhip_scene_update_instances
+ * keeps them (the topology stays).  *out_set is a handle of 16 or more, never reused.
+ * Returns 0.  2 = needs rayhip_scene_upload, nothing touched: no scene, the 8-wide tree, a tree of more than 128 levels, a handle that
+ * is not live, or (at create time) a range that holds a vertex of a triangle light while rayhip_scene_refit_lights is off (turning the
+ * switch off under such a set is an error).  1 = error: a null pointer, count == 0 or a range outside the array or overlapping a live
+ * set, a seventeenth set, flags outside 1..3, a weld index >= count or not canonical, more than 2^32 - 1 row entries. */
+#define RAYHIP_NORMALS_N 1u   /* recompute normals */
+#define RAYHIP_NORMALS_B 2u   /* recompute bitangents (from the uvs, as the reference's scene build does) */
+typedef struct rayhip_normals_desc {
+    uint32_t first_vertex, count;  /* range of the uploaded vertex array */
+    uint32_t flags;                /* RAYHIP_NORMALS_N | RAYHIP_NORMALS_B, at least one */
+    const uint32_t *weld;          /* NULL, or count indices RELATIVE to first_vertex: weld[i] is the canonical vertex of i's smoothing
+                                      group (weld[weld[i]] == weld[i]); normals only */
+} rayhip_normals_desc;
+RAYHIP_API int rayhip_normals_create(rayhip_ctx *ctx, const rayhip_normals_desc *desc, int *out_set);
+RAYHIP_API int rayhip_normals_destroy(rayhip_ctx *ctx, int set);
+
 /* Emissive meshes that deform: 0 = off (default): unchanged behaviour.  1 = vertex updates and poses may move triangle lights.
  * With the switch on, rayhip_scene_update_vertices[_blob|_device] accept changed vertices of triangle lights, rayhip_skin_create accepts
  * ranges that hold such vertices, and every vertex update or pose refits ON THE DEVICE, behind the geometry and before it returns

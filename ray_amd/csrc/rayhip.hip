@@ -32,6 +32,7 @@
 #include "refit.hip.h"
 #include "skin.hip.h"
 #include "morph.hip.h"
+#include "normals.hip.h"
 #include "light_refit.hip.h"
 #include "scene_blob.h"
 #include "scene_rebuild.h"

@@ -219,6 +219,31 @@ struct rayhip_ctx {
             m.base.release(), m.row.release(), m.entries.release();
         }
     }
+    // normal sets (rayhip_normals_create, normals.h): the faces of a vertex range and its row tables, on the device until the next scene
+    // upload; every call that writes the vertex array recomputes n and / or b of the range behind its copy (recompute_normal_sets)
+    struct Normals {
+        bool live = false;
+        int id = 0; // the handle the caller holds, made as a skin's
+        uint32_t first = 0, count = 0, flags = 0, faces_count = 0;
+        bool welded = false;
+        DevBuf faces, row, entries, wrow, wentries; // uint32 [faces_count], [count + 1], [row[count]]; of a welded set [count + 1], [wrow[count]]
+        DevBuf frames;                              // rayhip_normals::FaceFrame [faces_count]: scratch of the two kernels
+    } normal_sets[rayhip_normals::MAX_SETS];
+    uint32_t normals_serial = 0;
+    // the live normal set handle `id` names, or null
+    Normals *normals_of(const int id) {
+        Normals &n = normal_sets[id & int(rayhip_normals::MAX_SETS - 1)];
+        return id > 0 && n.live && n.id == id ? &n : nullptr;
+    }
+    static void release_normals(Normals &n) {
+        n.live = false;
+        n.faces.release(), n.row.release(), n.entries.release(), n.wrow.release(), n.wentries.release(), n.frames.release();
+    }
+    void discard_normals() {
+        for (Normals &n : normal_sets) {
+            release_normals(n);
+        }
+    }
     DevBuf skin_stage;    // the posed vertices of one rayhip_scene_pose[_skins] call, range after range (sized to the largest call seen)
     DevBuf skin_palettes; // ... and its palettes and morph weights
     DevBuf skin_counters; // [0] used vertices without a finite position, [1] changed light vertices
@@ -900,6 +925,7 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
     c->stack_spill2.release();
     c->discard_skins();
     c->discard_morphs();
+    c->discard_normals();
     for (DevBuf *b : {&c->refit.level_nodes, &c->refit.first_entry, &c->refit.scratch, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices,
                       &c->light_refit.level_nodes, &c->light_refit.leaf, &c->light_refit.node_summary, &c->light_refit.slot_scale, &c->skin_stage,
                       &c->skin_palettes, &c->skin_counters}) {

@@ -3,7 +3,8 @@
 // keep_light_vertices, upload_vertex_checks, prepare_light_refit), the phase stamps, the preconditions, the light refit and the
 // geometry refit behind new vertices, the entry points (rayhip_scene_update_vertices, its _blob and _device forms; refit.h), the
 // skins (rayhip_skin_create / _destroy, rayhip_scene_pose_skins; skin.h), the morph sets (rayhip_morph_create / _destroy,
-// rayhip_scene_pose; morph.h) and the switch (rayhip_scene_refit_lights; light_refit.h).
+// rayhip_scene_pose; morph.h), the normal sets (rayhip_normals_create / _destroy; normals.h: recomputed at the top of the geometry
+// refit) and the switch (rayhip_scene_refit_lights; light_refit.h).
 #pragma once
 
 // what the refit needs of the upload's half of the launcher (rayhip_upload.hip.h)
@@ -228,11 +229,43 @@ static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, const VertexStamp
 // the per-triangle vertex table (k_fill_tri_verts), the 4-wide collapse over the same root list, the instance boxes (host, from the root
 // nodes read back) and the top level (the path of rayhip_scene_update_instances).  refit.h / refit.hip.h.
 
+// the live normal sets (rayhip_normals_create; normals.h, normals.hip.h): n and / or b of every set's range recomputed in place from the
+// positions and uvs that are in the vertex array now -- every set, whatever range the call wrote, as the refit refits every tree.  The
+// sets do not depend on each other: a face record is made of positions and uvs, which no set writes.  Nothing is launched, stamped or
+// waited for while no set is live.
+static int recompute_normal_sets(rayhip_ctx *c, const VertexStamps &st) {
+    bool any = false;
+    for (const rayhip_ctx::Normals &n : c->normal_sets) {
+        if (!n.live) {
+            continue;
+        }
+        any = true;
+        if (n.faces_count == 0) {
+            continue; // (no tree reaches a triangle of the range: every record stays)
+        }
+        rayhip_normals::k_face_frames<<<(n.faces_count + 255) / 256, 256, 0, c->stream>>>(c->vertices.as<rayhip_vertex>(), c->vtx_indices.as<uint32_t>(),
+                                                                                         n.faces.as<uint32_t>(), n.faces_count,
+                                                                                         n.frames.as<rayhip_normals::FaceFrame>());
+        HIP_TRY(hipGetLastError());
+        rayhip_normals::k_vertex_frames<<<(n.count + 255) / 256, 256, 0, c->stream>>>(
+            c->vertices.as<rayhip_vertex>() + n.first, n.row.as<uint32_t>(), n.entries.as<uint32_t>(), n.welded ? n.wrow.as<uint32_t>() : nullptr,
+            n.welded ? n.wentries.as<uint32_t>() : nullptr, n.frames.as<rayhip_normals::FaceFrame>(), n.count, n.flags);
+        HIP_TRY(hipGetLastError());
+    }
+    if (any) {
+        HIP_TRY(st.stamp("normals recomputed"));
+    }
+    return 0;
+}
+
 // everything a vertex update recomputes once the new vertices are in c->vertices (in stream order behind them).  `st`: the caller's
 // stamps, for the start of the call; the lines written from here name rayhip_scene_update_vertices whichever entry point called
 // (tools/vertex_update_bench.py reads the phases by that prefix)
 static int refit_after_vertices(rayhip_ctx *c, VertexStamps st) {
     st.who = "rayhip_scene_update_vertices";
+    if (recompute_normal_sets(c, st)) { // first: the table of k_fill_tri_verts, the light refit and the frames read the new n and b
+        return 1;
+    }
     rayhip_ctx::Refit &r = c->refit;
     hipStream_t s = c->stream;
     const uint32_t n_tris = c->geometry.vtx_indices / 3;
@@ -693,6 +726,95 @@ int rayhip_morph_destroy(rayhip_ctx *c, int morph) {
     return 0;
 }
 
+// ---- normal sets (normals.h, normals.hip.h) ---------------------------------------------------------------------------------------------------
+// The topology is read back once, here: the nodes, the entry table and the indices as they are on the device (the leaf refinement of an
+// upload changed the first two; the faces of a set are the triangles the device's own trees reach).
+int rayhip_normals_create(rayhip_ctx *c, const rayhip_normals_desc *d, int *out_set) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (!d || !out_set) {
+        return fail("rayhip_normals_create: a null pointer");
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_normals_create")) {
+        return rc;
+    }
+    if (d->count == 0 || uint64_t(d->first_vertex) + d->count > c->geometry.vertices) {
+        return outside_the_scene(c, "rayhip_normals_create", d->first_vertex, d->count);
+    }
+    int slot = -1;
+    for (int k = int(rayhip_normals::MAX_SETS) - 1; k >= 0; --k) {
+        const rayhip_ctx::Normals &o = c->normal_sets[k];
+        if (!o.live) {
+            slot = k;
+        } else if (d->first_vertex < o.first + o.count && o.first < d->first_vertex + d->count) {
+            return fail("rayhip_normals_create: vertices [%u, %u + %u) overlap normal set %d", d->first_vertex, d->first_vertex, d->count, o.id);
+        }
+    }
+    if (slot < 0) {
+        return fail("rayhip_normals_create: %u normal sets are live already", rayhip_normals::MAX_SETS);
+    }
+    {
+        uint32_t where = 0;
+        if (const int bad = rayhip_normals::validate_desc(d->count, d->flags, d->weld, where)) {
+            return bad == 1   ? fail("rayhip_normals_create: flags %u (RAYHIP_NORMALS_N | RAYHIP_NORMALS_B, at least one)", d->flags)
+                   : bad == 2 ? fail("rayhip_normals_create: the weld index of vertex %u is outside the range of %u", d->first_vertex + where, d->count)
+                              : fail("rayhip_normals_create: the weld index of vertex %u is not canonical (weld[weld[i]] != weld[i])", d->first_vertex + where);
+        }
+    }
+    if (const uint32_t *pinned = pinned_light_vertex(c, d->first_vertex, d->count, nullptr)) { // (the skins' rule)
+        (void)fail("rayhip_normals_create: vertex %u belongs to a triangle light; lights are not rebuilt by a recompute", *pinned);
+        return 2;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<rayhip_bvh2_node> nodes(c->nodes_used);
+    std::vector<uint32_t> tri_indices(c->refit.entries), vtx_indices(c->geometry.vtx_indices);
+    auto back = [&](void *dst, const DevBuf &src, const size_t bytes) { return bytes == 0 || hipMemcpy(dst, src.p, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    if (!back(nodes.data(), c->nodes, nodes.size() * sizeof(rayhip_bvh2_node)) || !back(tri_indices.data(), c->tri_indices, tri_indices.size() * sizeof(uint32_t)) ||
+        !back(vtx_indices.data(), c->vtx_indices, vtx_indices.size() * sizeof(uint32_t))) {
+        return fail("rayhip_normals_create: reading the topology back failed");
+    }
+    std::vector<uint32_t> reachable;
+    if (!rayhip_normals::reachable_triangles(nodes.data(), uint32_t(nodes.size()), c->refit.roots.data(), c->refit.roots.size(), tri_indices.data(),
+                                             uint32_t(tri_indices.size()), vtx_indices.data(), uint32_t(vtx_indices.size() / 3), c->geometry.vertices, reachable)) {
+        return fail("rayhip_normals_create: a bottom-level tree on the device is malformed");
+    }
+    rayhip_normals::Tables tb;
+    if (rayhip_normals::build_rows(reachable.data(), reachable.size(), vtx_indices.data(), d->first_vertex, d->count,
+                                   (d->flags & RAYHIP_NORMALS_N) ? d->weld : nullptr, tb)) {
+        return fail("rayhip_normals_create: more than 2^32 - 1 row entries");
+    }
+    rayhip_ctx::Normals &n = c->normal_sets[slot];
+    const bool welded = !tb.wrow.empty();
+    if (upload(c, n.faces, tb.faces.data(), tb.faces.size() * sizeof(uint32_t)) || upload(c, n.row, tb.row.data(), tb.row.size() * sizeof(uint32_t)) ||
+        upload(c, n.entries, tb.entries.data(), tb.entries.size() * sizeof(uint32_t)) ||
+        (welded && (upload(c, n.wrow, tb.wrow.data(), tb.wrow.size() * sizeof(uint32_t)) ||
+                    upload(c, n.wentries, tb.wentries.data(), tb.wentries.size() * sizeof(uint32_t)))) ||
+        n.frames.alloc(tb.faces.size() * sizeof(rayhip_normals::FaceFrame))) {
+        rayhip_ctx::release_normals(n);
+        return 1;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the tables go out of scope
+    c->normals_serial = (c->normals_serial % 0x7ffffffu) + 1; // (as a skin's handle)
+    n.live = true, n.id = int(c->normals_serial << 4) | slot, n.first = d->first_vertex, n.count = d->count, n.flags = d->flags;
+    n.faces_count = uint32_t(tb.faces.size()), n.welded = welded;
+    *out_set = n.id;
+    return 0;
+}
+
+int rayhip_normals_destroy(rayhip_ctx *c, int set) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (!c->normals_of(set)) {
+        (void)fail("rayhip_normals_destroy: normal set %d is not live", set);
+        return 2;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rayhip_ctx::release_normals(*c->normals_of(set));
+    return 0;
+}
+
 // Morph sets and skins in one pose.  A skin's range is staged as a sequence of launches over segments -- [plain][set A][plain][set B]... --
 // plain ones by k_skin_vertices with its pointers offset, covered ones by the fused kernel: no kernel looks for the set it is in.
 int rayhip_scene_pose(rayhip_ctx *c, int n_morphs, const int *morphs, const float *const *weights, int n_skins, const int *skins, const float *const *palettes) {
@@ -858,6 +980,13 @@ int rayhip_scene_refit_lights(rayhip_ctx *c, int on) {
             for (const auto &kept : c->refit.light_vertices) {
                 if (m.live && kept.first >= m.first && kept.first - m.first < m.count) {
                     return fail("rayhip_scene_refit_lights: morph set %d covers vertex %u of a triangle light; destroy it first", m.id, kept.first);
+                }
+            }
+        }
+        for (const rayhip_ctx::Normals &n : c->normal_sets) {
+            for (const auto &kept : c->refit.light_vertices) {
+                if (n.live && kept.first >= n.first && kept.first - n.first < n.count) {
+                    return fail("rayhip_scene_refit_lights: normal set %d covers vertex %u of a triangle light; destroy it first", n.id, kept.first);
                 }
             }
         }

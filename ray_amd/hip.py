@@ -89,6 +89,12 @@ class MorphDesc(C.Structure):  # rayhip_morph_desc
                 ("targets", C.POINTER(MorphTarget))]
 
 
+class NormalsDesc(C.Structure):  # rayhip_normals_desc
+    _fields_ = [("first_vertex", C.c_uint32), ("count", C.c_uint32), ("flags", C.c_uint32), ("weld", C.c_void_p)]
+
+
+NORMALS_N, NORMALS_B = 1, 2  # RAYHIP_NORMALS_N / _B
+
 CACHE_ENTRIES = 1 << 22  # slots of the spatial cache's key table (rt_cache.h)
 # rayhip_cache_vertex: one vertex of a cache-update bounce
 CACHE_VERTEX_DTYPE = np.dtype([("o", "<f4", 3), ("t", "<f4"), ("d", "<f4", 3), ("path", "<u4"), ("n", "<f4", 3), ("ends", "<u4"),
@@ -111,7 +117,7 @@ assert LIGHT_NODE_DTYPE.itemsize == 208
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "scene_refit_lights", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "normals_create", "normals_destroy", "scene_refit_lights", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
@@ -127,6 +133,23 @@ def _aligned_copy(buf: bytes, align: int = 64) -> np.ndarray:
     off = (-raw.ctypes.data) % align
     out = raw[off:off + len(buf)]
     out[:] = np.frombuffer(buf, dtype=np.uint8)
+    return out
+
+
+def weld_by_position(positions) -> np.ndarray:
+    """uint32 [count]: per vertex the lowest index among the vertices whose position is bytewise equal to its own -- the `weld` of
+    Context.create_normals for a range whose smoothing groups are its coincident vertices (the twins a scene build appends when it
+    derives bitangents are such)"""
+    p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    if len(p) == 0:
+        return np.zeros(0, dtype=np.uint32)
+    keys = p.view(np.uint32)
+    order = np.lexsort((np.arange(len(p)), keys[:, 2], keys[:, 1], keys[:, 0]))  # equal keys together, ascending index within them
+    sorted_keys = keys[order]
+    starts = np.r_[True, np.any(sorted_keys[1:] != sorted_keys[:-1], axis=1)]
+    lowest = order[np.flatnonzero(starts)][np.cumsum(starts) - 1]
+    out = np.empty(len(p), dtype=np.uint32)
+    out[order] = lowest
     return out
 
 
@@ -219,6 +242,8 @@ class Library:
             f("morph_create").argtypes = [vp, C.POINTER(MorphDesc), C.POINTER(C.c_int)]
             f("morph_destroy").argtypes = [vp, C.c_int]
             f("scene_pose").argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(vp), C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
+            f("normals_create").argtypes = [vp, C.POINTER(NormalsDesc), C.POINTER(C.c_int)]
+            f("normals_destroy").argtypes = [vp, C.c_int]
             f("scene_refit_lights").argtypes = [vp, C.c_int]
 
     def fn(self, name):
@@ -433,6 +458,29 @@ class Context:
         c_k = (C.c_int * max(len(k_ids), 1))(*k_ids)
         c_p = (C.c_void_p * max(len(k_ids), 1))(*[a.ctypes.data for a in p])
         rc = self.L.fn("scene_pose")(self._ctx, len(m_ids), c_m, c_w, len(k_ids), c_k, c_p)
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def create_normals(self, first: int, count: int, normals: bool = True, bitangents: bool = True, weld=None) -> int:
+        """a normal set over vertices [first, first + count) (rayhip_normals_create): while it is live, every vertex update and pose
+        recomputes the normals and / or bitangents of the range on the device from the positions then in the vertex array.  `weld`: None,
+        or [count] uint32 relative to `first`, the canonical vertex of each vertex's smoothing group (weld_by_position).  Returns the
+        set's id (16 or more), or 2 where the ABI returns 2; an error raises."""
+        if weld is not None:
+            weld = np.ascontiguousarray(weld, dtype=np.uint32)
+            assert weld.shape == (count,)
+        d = NormalsDesc(int(first), int(count), (NORMALS_N if normals else 0) | (NORMALS_B if bitangents else 0), weld.ctypes.data if weld is not None else None)
+        out = C.c_int(-1)
+        rc = self.L.fn("normals_create")(self._ctx, C.byref(d), C.byref(out))
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return int(out.value)
+
+    def destroy_normals(self, handle: int) -> int:
+        rc = self.L.fn("normals_destroy")(self._ctx, int(handle))
         if rc == 2:
             return 2
         self.L.check(rc)
