@@ -553,10 +553,31 @@ RAYHIP_API int rayhip_normals_destroy(rayhip_ctx *ctx, int set);
  * lights on the device describe at that moment. */
 RAYHIP_API int rayhip_scene_refit_lights(rayhip_ctx *ctx, int on);
 
+/* INSTANCES THAT MOVE (a door, a wheel, a thousand crates): new transforms for n instance slots of the uploaded scene, and nothing
+ * else -- no host scene, no rayhip_scene_desc (ray_amd/csrc/instances.h, instances.hip.h).  xforms[i] (16 floats, the layout of
+ * rayhip_mesh_instance::xform / SceneBase::SetMeshInstanceTransform) belongs to slots[i].  On the device, before the call returns:
+ * xform and inv_xform of the named records (bytes 16..143 of the 144; mesh_index, node_index, lights_index and ray_visibility stay),
+ * inv_xform being the reference's InverseMatrix operation for operation, i.e. the bits SetMeshInstanceTransform stores; the world box
+ * of EVERY live slot, from the root node of its bottom-level tree as it is on the device now (a mesh that was deformed moves with its
+ * deformed box; the box arithmetic is the vertex update's, so "move, then pose" and "pose, then move" leave the same bytes); the top
+ * level over those boxes and, with rayhip_scene_refit_lights on, the triangle lights that hang on a named slot and the light tree,
+ * topology kept, as after a vertex update.  Meshes, trees, materials, skins, morph sets and normal sets live in object space and stay.
+ * The call waits for pending passes first; the accumulated image is the caller's to clear.  Everything is checked before anything on
+ * the device is written -- a refused call has touched nothing.  Returns 0; 1 = a null pointer with n > 0, a slot outside the instance
+ * array, one the top level does not name (a freed slot of the pool) or one named twice, a matrix with an element that is not finite or
+ * whose inverse has one (a singular matrix); 2 = the scene needs rayhip_scene_upload: there is none, the context walks the 8-wide tree,
+ * or a named slot carries triangle lights while rayhip_scene_refit_lights is off (a transform bytewise equal to the one in place
+ * passes).  n == 0 returns 0 and launches nothing.  A later rayhip_scene_update_instances replaces everything by the host's arrays. */
+RAYHIP_API int rayhip_scene_set_instance_transforms(rayhip_ctx *ctx, uint32_t n, const uint32_t *slots, const float *xforms);
+/* the same from DEVICE memory of the context's device (the caller's own physics kernels, a tensor), complete when the call is made
+ * and unchanged until it returns.  A matrix array that is 16-byte aligned is read with 16-byte loads. */
+RAYHIP_API int rayhip_scene_set_instance_transforms_device(rayhip_ctx *ctx, uint32_t n, const uint32_t *device_slots, const float *device_xforms);
+
 /* test hook: copy a device array of the acceleration structure to the host. which: 0 BVH2 nodes [0, nodes_used),
  * 1 tris as 48-byte records (un-pitched), 2 tri_indices, 3 the live top-level leaves as (instance slot, lo.xyz, hi.xyz) 7 x 4 bytes each,
  * 4 the vertex array as 44-byte records, 5 the light tree (light_cwnodes, 208 bytes each), 6 its importance rows (light_children,
- * 26 x 16 bytes per node), 7 the world-space corners of the triangle lights (light_tri_geom, 4 x 16 bytes per light slot) */
+ * 26 x 16 bytes per node), 7 the world-space corners of the triangle lights (light_tri_geom, 4 x 16 bytes per light slot),
+ * 8 the instance array (144 bytes per slot) */
 RAYHIP_API int rayhip_k_read_accel(rayhip_ctx *ctx, int which, void *dst, size_t capacity_bytes, size_t *out_bytes);
 
 /* 1024-entry inverse filter CDF (RendererCPU.h:1234-1258 UpdateFilterTable; upload RendererVK.cpp:386-424) */

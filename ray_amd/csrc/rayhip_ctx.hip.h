@@ -166,6 +166,10 @@ struct rayhip_ctx {
         // ... and what the updates that never see the vertices on the host check on the device (skin.hip.h)
         DevBuf d_vertex_used;                     // vertex_used
         DevBuf d_light_index, d_light_vertices;   // light_vertices as two arrays
+        // ... and what a call that moves instances checks its slots against (instances.h): per slot of the instance array SLOT_LIVE |
+        // SLOT_TRI_LIGHTS, the same on the device with `live`, and one claim word per slot
+        std::vector<uint8_t> slot_flags;
+        DevBuf d_slot_flags, d_live, d_slot_claim;
     } refit;
     // rayhip_scene_refit_lights (light_refit.h): what a vertex update needs to refit the lights, prepared by whichever comes second of
     // the switch and the upload, and again by an instance update
@@ -247,6 +251,9 @@ struct rayhip_ctx {
     DevBuf skin_stage;    // the posed vertices of one rayhip_scene_pose[_skins] call, range after range (sized to the largest call seen)
     DevBuf skin_palettes; // ... and its palettes and morph weights
     DevBuf skin_counters; // [0] used vertices without a finite position, [1] changed light vertices
+    // one rayhip_scene_set_instance_transforms call: the staged 128-byte records of the named slots, the slots, the boxes of the live
+    // slots (one block, read back in one copy); a copy of the caller's host arrays; the findings and the lights without area
+    DevBuf instance_stage, instance_args, instance_counters;
     // ---- (deforming: end) ----
     bool adaptive_dirty = false; // a pass ran with variance_threshold != 0 since the last Clear / Resize: required_samples may
                                  // lie below the next iteration, so passes are not batched (rayhip_render_batch)
@@ -928,7 +935,8 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
     c->discard_normals();
     for (DevBuf *b : {&c->refit.level_nodes, &c->refit.first_entry, &c->refit.scratch, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices,
                       &c->light_refit.level_nodes, &c->light_refit.leaf, &c->light_refit.node_summary, &c->light_refit.slot_scale, &c->skin_stage,
-                      &c->skin_palettes, &c->skin_counters}) {
+                      &c->skin_palettes, &c->skin_counters, &c->refit.d_slot_flags, &c->refit.d_live, &c->refit.d_slot_claim, &c->instance_stage,
+                      &c->instance_args, &c->instance_counters}) {
         b->release();
     }
     for (hipEvent_t e : c->events) {

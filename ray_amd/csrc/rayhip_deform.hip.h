@@ -1,7 +1,8 @@
 // rayhip_deform.hip.h -- part of librayhip's host side (one translation unit: included by rayhip.hip before rayhip_upload.hip.h):
 // deforming a scene that is on the device.  In reading order: the tables an upload or instance update leaves behind (prepare_refit,
-// keep_light_vertices, upload_vertex_checks, prepare_light_refit), the phase stamps, the preconditions, the light refit and the
-// geometry refit behind new vertices, the entry points (rayhip_scene_update_vertices, its _blob and _device forms; refit.h), the
+// keep_light_vertices, upload_vertex_checks, upload_instance_checks, prepare_light_refit), the phase stamps, the preconditions, the light
+// refit and the geometry refit behind new vertices, the entry points (rayhip_scene_update_vertices, its _blob and _device forms; refit.h),
+// the instances that move (rayhip_scene_set_instance_transforms and its _device form; instances.h), the
 // skins (rayhip_skin_create / _destroy, rayhip_scene_pose_skins; skin.h), the morph sets (rayhip_morph_create / _destroy,
 // rayhip_scene_pose; morph.h), the normal sets (rayhip_normals_create / _destroy; normals.h: recomputed at the top of the geometry
 // refit) and the switch (rayhip_scene_refit_lights; light_refit.h).
@@ -100,6 +101,35 @@ static int upload_vertex_checks(rayhip_ctx *c, const bool with_used) {
         return 1;
     }
     HIP_TRY(hipStreamSynchronize(c->stream)); // the two vectors go out of scope
+    return 0;
+}
+
+// ... and what a call that moves instances checks its slots against (rayhip_scene_set_instance_transforms; instances.h, k_pose_instances):
+// per slot of the instance array whether the top level names it (refit.live, refit.instances: set before this is called) and whether a
+// triangle light hangs on it, on the host and on the device, with the live slots and one claim word per slot.  `d`: the light arrays.
+static int upload_instance_checks(rayhip_ctx *c, const rayhip_scene_desc *d) {
+    rayhip_ctx::Refit &r = c->refit;
+    r.slot_flags.assign(r.instances.size(), 0);
+    for (const uint32_t mi : r.live) {
+        if (mi < r.slot_flags.size()) {
+            r.slot_flags[mi] |= uint8_t(rayhip_instances::SLOT_LIVE);
+        }
+    }
+    for (uint32_t k = 0; k < d->li_indices_count; ++k) {
+        const uint32_t i = d->li_indices[k];
+        if (i >= d->lights_count || light_type(d->lights[i]) != LIGHT_TYPE_TRI) {
+            continue;
+        }
+        const uint32_t mi = float_as_uint(d->lights[i].params[1]);
+        if (mi < r.slot_flags.size()) {
+            r.slot_flags[mi] |= uint8_t(rayhip_instances::SLOT_TRI_LIGHTS);
+        }
+    }
+    if (upload(c, r.d_slot_flags, r.slot_flags.data(), r.slot_flags.size()) || upload(c, r.d_live, r.live.data(), r.live.size() * sizeof(uint32_t)) ||
+        r.d_slot_claim.alloc(r.slot_flags.size() * sizeof(uint32_t)) || hipStreamSynchronize(c->stream) != hipSuccess) {
+        r.slot_flags.clear(); // (no table on the device: a call that moves instances says that it needs an upload)
+        return fail("the per-slot table of the instances could not be uploaded");
+    }
     return 0;
 }
 
@@ -470,6 +500,159 @@ int rayhip_scene_update_vertices_device(rayhip_ctx *c, uint32_t first_vertex, ui
     }
     HIP_TRY(st.stamp("vertices copied"));
     return refit_after_vertices(c, st);
+}
+
+// ---- moving instances: transforms in, inverses and world boxes on the device, the top level rebuilt (instances.h, instances.hip.h) ----
+// Meshes, trees, materials, skins, morph sets and normal sets live in object space and stay.  k_pose_instances stages the new records
+// and counts what is wrong with the call; only when its counters came back zero are the records scattered into the instance array
+// (k_commit_instances), the boxes of EVERY live slot recomputed from the root nodes as they are on the device now (k_instance_boxes: a
+// deformed mesh moves with its deformed box), the lights re-placed when a named slot carries some (the switch is on, or the call was
+// refused), and the top level rebuilt by the path of the vertex update.  The kernels are tiny: the call is bound by its launches, its
+// two read-backs and the top-level build.
+// `d_slots` / `d_xforms`: device memory, complete and stable until the call returns.
+static int set_instance_transforms(rayhip_ctx *c, const VertexStamps &st, const uint32_t n, const uint32_t *d_slots, const float *d_xforms) {
+    namespace ri = rayhip_instances;
+    rayhip_ctx::Refit &r = c->refit;
+    hipStream_t s = c->stream;
+    const uint32_t n_live = uint32_t(r.live.size());
+    // one block, read back in one copy: [n] staged records of 128 bytes, [n_live] boxes of 24 bytes, [n] slots
+    const size_t boxes_at = size_t(n) * 128, slots_at = (boxes_at + size_t(n_live) * 24 + 15) & ~size_t(15), stage_bytes = slots_at + size_t(n) * 4;
+    if (c->instance_stage.alloc(stage_bytes) || c->instance_counters.alloc(8 * sizeof(uint32_t))) {
+        return 1;
+    }
+    float4 *d_staged = c->instance_stage.as<float4>();
+    float *d_boxes = reinterpret_cast<float *>(c->instance_stage.as<uint8_t>() + boxes_at);
+    uint32_t *d_staged_slots = reinterpret_cast<uint32_t *>(c->instance_stage.as<uint8_t>() + slots_at);
+    uint32_t *d_counters = c->instance_counters.as<uint32_t>(); // ([N_FINDINGS]: triangle lights without area)
+    rayhip_mesh_instance *d_instances = c->mesh_instances.as<rayhip_mesh_instance>();
+    HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint32_t), s));
+    if (!r.slot_flags.empty()) {
+        HIP_TRY(hipMemsetAsync(r.d_slot_claim.p, 0, r.slot_flags.size() * sizeof(uint32_t), s));
+    }
+    ri::k_pose_instances<<<(n + 255) / 256, 256, 0, s>>>(d_slots, d_xforms, n, (reinterpret_cast<uintptr_t>(d_xforms) & 15u) == 0u, r.d_slot_flags.as<uint8_t>(),
+                                                        r.d_slot_claim.as<uint32_t>(), d_instances, c->instances_count, !c->light_refit.on, d_staged,
+                                                        d_staged_slots, d_counters);
+    HIP_TRY(hipGetLastError());
+    uint32_t findings[ri::N_FINDINGS] = {};
+    HIP_TRY(hipMemcpyAsync(findings, d_counters, sizeof(findings), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (findings[ri::BAD_SLOT] != 0) {
+        return fail("%s: %u of the slots are outside the %u instance slots, or not in the top level", st.who, findings[ri::BAD_SLOT], c->instances_count);
+    }
+    if (findings[ri::DUPLICATE] != 0) {
+        return fail("%s: %u slots are named more than once", st.who, findings[ri::DUPLICATE]);
+    }
+    if (findings[ri::NOT_FINITE] != 0) {
+        return fail("%s: %u transforms have an element that is not finite, or an inverse that has one (a singular matrix)", st.who, findings[ri::NOT_FINITE]);
+    }
+    if (findings[ri::PINNED] != 0) {
+        (void)fail("%s: %u of the slots carry triangle lights; lights are not rebuilt by this call (rayhip_scene_refit_lights)", st.who, findings[ri::PINNED]);
+        return 2;
+    }
+    // (the counters are back and zero: from here on the live instance array is written)
+    ri::k_commit_instances<<<(n + 255) / 256, 256, 0, s>>>(d_staged, d_staged_slots, n, d_instances, c->instances_count);
+    HIP_TRY(hipGetLastError());
+    if (n_live) {
+        ri::k_instance_boxes<<<(n_live + 255) / 256, 256, 0, s>>>(r.d_live.as<uint32_t>(), n_live, d_instances, c->instances_count, c->nodes.as<rayhip_bvh2_node>(),
+                                                                c->nodes_used, d_boxes);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<uint8_t> back(stage_bytes);
+    HIP_TRY(hipMemcpyAsync(back.data(), c->instance_stage.p, stage_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(st.stamp("instances posed"));
+    // the host's copy of the instance array follows: the source of the direct entry's arguments and of a later vertex update's boxes
+    bool lights_moved = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t slot = 0;
+        memcpy(&slot, back.data() + slots_at + size_t(i) * 4, sizeof(slot));
+        memcpy(r.instances[slot].xform, back.data() + size_t(i) * 128, 128); // (xform and inv_xform lie side by side)
+        lights_moved = lights_moved || (r.slot_flags[slot] & ri::SLOT_TRI_LIGHTS) != 0;
+    }
+    if (lights_moved && c->light_refit.on) { // the triangle lights are re-placed by the instance array that is on the device now
+        if (refit_lights(c, d_counters + ri::N_FINDINGS, st)) {
+            return 1;
+        }
+        HIP_TRY(hipMemcpyAsync(&c->light_refit.degenerate, d_counters + ri::N_FINDINGS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    rayhip_update::Plan up;
+    up.live = r.live;
+    up.boxes.resize(n_live);
+    if (n_live) {
+        memcpy(up.boxes.data(), back.data() + boxes_at, size_t(n_live) * sizeof(rayhip_lbvh::Box));
+    }
+    uint32_t tlas_root = 0xffffffffu;
+    rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
+    if (const int rc = rebuild_top_level(c, up, tlas_root, root_box)) {
+        return rc == 2 ? fail("%s: %s", st.who, std::string(g_err).c_str()) : rc; // (the instance array is the new one already: an error)
+    }
+    refresh_top_level_view(c, tlas_root, root_box, n_live);
+    HIP_TRY(st.stamp("top level built"));
+    return 0;
+}
+
+// what both forms check before anything else: 0 = go on, 1 / 2 = the return code
+static int instance_move_possible(rayhip_ctx *c, const char *who, const uint32_t n, const void *slots, const void *xforms) {
+    if (n > 0 && (!slots || !xforms)) {
+        return fail("%s: a null pointer", who);
+    }
+    if (!c->have_scene) {
+        (void)fail("%s before rayhip_scene_upload", who);
+        return 2;
+    }
+    if (c->wide == 8) {
+        (void)fail("%s: the context walks the 8-wide tree, whose builder runs on the host only", who);
+        return 2;
+    }
+    if (c->refit.slot_flags.size() != c->instances_count || c->refit.instances.size() != c->instances_count) { // (an upload that failed half-way)
+        (void)fail("%s: the tables of the last upload are incomplete", who);
+        return 2;
+    }
+    if (c->light_refit.on && !c->light_refit.ready) {
+        return fail("%s: rayhip_scene_refit_lights is on, but its tables are not prepared", who);
+    }
+    return 0;
+}
+
+int rayhip_scene_set_instance_transforms(rayhip_ctx *c, uint32_t n, const uint32_t *slots, const float *xforms) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (const int rc = instance_move_possible(c, "rayhip_scene_set_instance_transforms", n, slots, xforms)) {
+        return rc;
+    }
+    if (n == 0) {
+        return 0;
+    }
+    const VertexStamps st{c, "rayhip_scene_set_instance_transforms"};
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    // the caller's arrays onto the device: [n] matrices, [n] slots
+    if (c->instance_args.alloc(size_t(n) * 68)) {
+        return 1;
+    }
+    float *d_xforms = c->instance_args.as<float>();
+    uint32_t *d_slots = reinterpret_cast<uint32_t *>(c->instance_args.as<uint8_t>() + size_t(n) * 64);
+    HIP_TRY(hipMemcpyAsync(d_xforms, xforms, size_t(n) * 64, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_slots, slots, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
+    return set_instance_transforms(c, st, n, d_slots, d_xforms); // (it waits for the stream before it returns: the arrays may go away)
+}
+
+int rayhip_scene_set_instance_transforms_device(rayhip_ctx *c, uint32_t n, const uint32_t *device_slots, const float *device_xforms) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (const int rc = instance_move_possible(c, "rayhip_scene_set_instance_transforms_device", n, device_slots, device_xforms)) {
+        return rc;
+    }
+    if (n == 0) {
+        return 0;
+    }
+    const VertexStamps st{c, "rayhip_scene_set_instance_transforms_device"};
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    return set_instance_transforms(c, st, n, device_slots, device_xforms);
 }
 
 // ---- the skins ---------------------------------------------------------------------------------------------------------------------------

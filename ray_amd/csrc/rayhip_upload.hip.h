@@ -611,7 +611,7 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
         return 1;
     }
     keep_light_vertices(c, d); // (... and what a vertex update checks against them: rayhip_deform.hip.h)
-    if (upload_vertex_checks(c, true)) {
+    if (upload_vertex_checks(c, true) || upload_instance_checks(c, d)) {
         return 1;
     }
     trace("lights done");
@@ -746,6 +746,9 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
     }
     c->refit.live = live, c->refit.instances = mis; // (what a later rayhip_scene_update_vertices rebuilds the top level over, and the direct entry's source)
     refresh_scene_view(c, d, tlas_root, root_box, uint32_t(live.size()));
+    if (upload_instance_checks(c, d)) { // (... and what a later rayhip_scene_set_instance_transforms checks its slots against)
+        return 1;
+    }
     trace("instances updated");
     return 0;
 }
@@ -874,6 +877,8 @@ int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_byt
         src = c->light_children.p, bytes = size_t(c->light_refit.nodes_count) * LIGHT_CHILDREN_STRIDE * sizeof(float4);
     } else if (which == 7) {
         src = c->light_tri_geom.p, bytes = size_t(c->light_refit.lights_count) * 4 * sizeof(float4);
+    } else if (which == 8) {
+        src = c->mesh_instances.p, bytes = size_t(c->instances_count) * sizeof(rayhip_mesh_instance);
     } else {
         return fail("rayhip_k_read_accel: no array %d", which);
     }

@@ -113,11 +113,14 @@ LIGHT_NODE_DTYPE = np.dtype([("bbox_min", "<f4", 3), ("_unused0", "<f4"), ("bbox
                              ("ch_bbox_max", "u1", (3, 8)), ("child", "<u4", 8), ("flux", "<f4", 8), ("axis", "<u4", 8),
                              ("cos_omega_ne", "<u4", 8)])  # rayhip_light_cwbvh_node
 assert LIGHT_NODE_DTYPE.itemsize == 208
+MESH_INSTANCE_DTYPE = np.dtype([("mesh_index", "<u4"), ("node_index", "<u4"), ("lights_index", "<u4"), ("ray_visibility", "<u4"),
+                                ("xform", "<f4", 16), ("inv_xform", "<f4", 16)])  # rayhip_mesh_instance
+assert MESH_INSTANCE_DTYPE.itemsize == 144
 
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "normals_create", "normals_destroy", "scene_refit_lights", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "normals_create", "normals_destroy", "scene_refit_lights", "scene_set_instance_transforms", "scene_set_instance_transforms_device", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
@@ -245,6 +248,8 @@ class Library:
             f("normals_create").argtypes = [vp, C.POINTER(NormalsDesc), C.POINTER(C.c_int)]
             f("normals_destroy").argtypes = [vp, C.c_int]
             f("scene_refit_lights").argtypes = [vp, C.c_int]
+            f("scene_set_instance_transforms").argtypes = [vp, u32, vp, vp]
+            f("scene_set_instance_transforms_device").argtypes = [vp, u32, vp, vp]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -493,11 +498,33 @@ class Context:
         self.L.check(self.L.fn("scene_refit_lights")(self._ctx, 1 if on else 0))
         return 0
 
+    def set_instance_transforms(self, slots, xforms) -> int:
+        """new transforms for the instance slots `slots` of the uploaded scene: `xforms` [n][16] float32 in the layout of
+        rayhip_mesh_instance::xform; inverses, world boxes and the top level follow on the device
+        (rayhip_scene_set_instance_transforms).  Returns as update_vertices(): 0, or 2 where the ABI returns 2; an error raises."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32).ravel()
+        xforms = np.ascontiguousarray(xforms, dtype=np.float32).reshape(-1, 16)
+        assert len(slots) == len(xforms)
+        rc = self.L.fn("scene_set_instance_transforms")(self._ctx, len(slots), slots.ctypes.data, xforms.ctypes.data)
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def set_instance_transforms_device(self, n: int, slots_pointer: int, xforms_pointer: int) -> int:
+        """the same from `n` uint32 slots and `n` x 16 float32 that are on this context's device already: their addresses as ints (a
+        tensor's data_ptr(), say), the data complete when the call is made (rayhip_scene_set_instance_transforms_device)"""
+        rc = self.L.fn("scene_set_instance_transforms_device")(self._ctx, int(n), C.c_void_p(int(slots_pointer)), C.c_void_p(int(xforms_pointer)))
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
     def read_accel(self, which: int) -> np.ndarray:
         """test hook (rayhip_k_read_accel): 0 the BVH2 nodes [n][16] u32 words, 1 the triangle records [n][12] f32, 2 tri_indices [n] u32,
         3 the live top-level leaves [n][7] u32 words (instance slot, lo.xyz, hi.xyz as float bits), by slot, 4 the vertex array as
         VERTEX_DTYPE records, 5 the light tree as LIGHT_NODE_DTYPE records (208 bytes each), 6 its importance rows [nodes][26][4] f32,
-        7 the world-space corners of the triangle lights [light slots][4][4] f32"""
+        7 the world-space corners of the triangle lights [light slots][4][4] f32, 8 the instance array as MESH_INSTANCE_DTYPE records"""
         n = C.c_size_t(0)
         self.L.fn("k_read_accel")(self._ctx, which, None, 0, C.byref(n))  # (refused: the size comes back)
         buf = np.zeros(max(int(n.value), 4) // 4, dtype=np.uint32)
@@ -505,7 +532,7 @@ class Context:
         buf = buf[:n.value // 4]
         return {0: lambda: buf.reshape(-1, 16), 1: lambda: buf.view(np.float32).reshape(-1, 12), 2: lambda: buf, 3: lambda: buf.reshape(-1, 7),
                 4: lambda: buf.view(VERTEX_DTYPE), 5: lambda: buf.view(LIGHT_NODE_DTYPE), 6: lambda: buf.view(np.float32).reshape(-1, 26, 4),
-                7: lambda: buf.view(np.float32).reshape(-1, 4, 4)}[which]()
+                7: lambda: buf.view(np.float32).reshape(-1, 4, 4), 8: lambda: buf.view(MESH_INSTANCE_DTYPE)}[which]()
 
     def render(self, iteration: int, rect=None, cam: Camera = None, flags: int = 0, stats: Stats = None):
         rect = (0, 0, self.w, self.h) if rect is None else rect
