@@ -573,11 +573,34 @@ RAYHIP_API int rayhip_scene_set_instance_transforms(rayhip_ctx *ctx, uint32_t n,
  * and unchanged until it returns.  A matrix array that is 16-byte aligned is read with 16-byte loads. */
 RAYHIP_API int rayhip_scene_set_instance_transforms_device(rayhip_ctx *ctx, uint32_t n, const uint32_t *device_slots, const float *device_xforms);
 
+/* ANALYTIC LIGHTS THAT MOVE OR CHANGE COLOUR (a lamp that swings, a spot that turns, a rect light that dims, a sun that moves): new
+ * records for n light slots of the uploaded scene, and nothing else -- no host scene, no rayhip_scene_desc (ray_amd/csrc/light_pose.h,
+ * light_pose.hip.h).  records[i] is a complete rayhip_light, the layout of rayhip_scene_desc::lights, and replaces light slot slots[i]:
+ * colour and the 12 parameter floats may change, word 0 (type, doublesided, cast_shadow, visible, sky_portal, ray_visibility) must be
+ * bytewise the word the slot holds, so the counts of visible and blocker lights and the choice of kernels stay.  Sphere, spot,
+ * directional, line, rect and disk lights; triangle lights follow their vertices and instances, the environment light needs an upload.
+ * On the device, before the call returns: the records; the leaf summaries of the named lights (box, axis and angles as the scene build
+ * computes them, flux = ((r + g) + b) * area as RebuildLightTree_nolock); the light tree, topology kept, refitted height by height as
+ * after a vertex update -- node boxes, quantised child boxes, flux, cone axis and cosines (a directional light's emission cosine is the
+ * record's own cos_angle) and the importance rows.  The leaf of a light this call replaced takes its flux and cone from its summary in
+ * every later refit, until an upload or an instance update brings the host's tree.  The call needs rayhip_scene_refit_lights on: the
+ * switch is what keeps the tree refittable.  It waits for pending passes first; the accumulated image is the caller's to clear.
+ * Everything is checked before anything on the device is written -- a refused call has touched nothing.  Returns 0; 1 = a null pointer
+ * with n > 0, a slot outside the light array or one li_indices does not name (a freed slot of the pool, a directional light baked into
+ * the physical sky), a slot named twice, a held or new record that is a triangle or environment light, a word 0 that differs from the
+ * held one, a colour or parameter that is not finite; 2 = there is no scene, or rayhip_scene_refit_lights is off or its tables are not
+ * prepared.  n == 0 returns 0 and launches nothing.  A later rayhip_scene_update_instances replaces everything by the host's arrays. */
+RAYHIP_API int rayhip_scene_set_lights(rayhip_ctx *ctx, uint32_t n, const uint32_t *slots, const rayhip_light *records);
+/* the same from DEVICE memory of the context's device, complete when the call is made and unchanged until it returns.  A record array
+ * that is 16-byte aligned is read with 16-byte loads; it must be 4-byte aligned. */
+RAYHIP_API int rayhip_scene_set_lights_device(rayhip_ctx *ctx, uint32_t n, const uint32_t *device_slots, const rayhip_light *device_records);
+
 /* test hook: copy a device array of the acceleration structure to the host. which: 0 BVH2 nodes [0, nodes_used),
  * 1 tris as 48-byte records (un-pitched), 2 tri_indices, 3 the live top-level leaves as (instance slot, lo.xyz, hi.xyz) 7 x 4 bytes each,
  * 4 the vertex array as 44-byte records, 5 the light tree (light_cwnodes, 208 bytes each), 6 its importance rows (light_children,
  * 26 x 16 bytes per node), 7 the world-space corners of the triangle lights (light_tri_geom, 4 x 16 bytes per light slot),
- * 8 the instance array (144 bytes per slot) */
+ * 8 the instance array (144 bytes per slot), 9 the light array (64 bytes per slot), 10 the leaf summaries of the light refit (48 bytes
+ * per light slot: box lo / hi, flux, cone axis, omega_n, omega_e; needs rayhip_scene_refit_lights) */
 RAYHIP_API int rayhip_k_read_accel(rayhip_ctx *ctx, int which, void *dst, size_t capacity_bytes, size_t *out_bytes);
 
 /* 1024-entry inverse filter CDF (RendererCPU.h:1234-1258 UpdateFilterTable; upload RendererVK.cpp:386-424) */

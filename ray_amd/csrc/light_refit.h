@@ -11,13 +11,15 @@
 //                    box = min / max of the corners; n = cross(p2 - p1, p3 - p1) (each component a*b - c*d); len = sqrtf((nx*nx + ny*ny) + nz*nz);
 //                    flux = ((col.r + col.g) + col.b) * (0.5f * len); axis = n / len; omega_n = PI if doublesided else 0; omega_e = PI / 2.
 //                    A triangle without area (len is 0 or not finite): flux 0, axis (0, 1, 0) -- it can never be picked.
-//   other lights     do not move with vertices: computed once on the host (static_light_summary), flux taken from the uploaded tree.
+//   other lights     do not move with vertices: computed once on the host (static_light_summary), flux taken from the uploaded tree;
+//                    one that rayhip_scene_set_lights replaced (light_pose.h) is complete, flux included, and marked in `posed`.
 // Node N, slots in the order 0..7, a slot being empty when child[i] == 0x7fffffff:
 //   box      the union of the FINITE children's boxes (min / max: exact in any order); without a finite child bbox_min/max keep their bytes
 //   per slot finite child: ch_bbox_min = floorf(q(lo)), ch_bbox_max = ceilf(q(hi)), q(v) = clamp((255 * (v - nlo)) / (nhi - nlo), 0, 255) and
 //            0 where nlo == nhi; infinite child: min bytes 0xff, max bytes 0; empty slot: untouched.
 //            Triangle-light leaves and inner children also get flux, the octahedral axis and the two cosines (cos omega_n,
-//            max(cos omega_e, 0)); the slots of other lights keep those three words bytewise.
+//            max(cos omega_e, 0)), and so do the leaves of lights marked in `posed`; the slots of other lights keep those three
+//            words bytewise.
 //            The flux of an INNER child's slot is the child's summed flux times the slot's SCALE: the ratio of the flux the uploaded
 //            tree stores there to the sum a refit finds below it at the upload pose (slot_scales, once per upload).  The scene build
 //            does not store the sum in every inner slot -- it hands a node's flux on to the parent once the node's left child is
@@ -114,8 +116,10 @@ struct Slot {
 };
 
 // slot of a non-empty child with summary `c` under a node whose box is [nlo, nhi] (valid when some child is finite, which a finite
-// `c` implies).  `cone_too`: a triangle-light leaf or an inner child; `flux_scale`: the slot's scale (1 for a leaf: its flux goes in as it is).
-RT_HD void refit_slot(const Summary &c, const bool cone_too, const float flux_scale, const float nlo[3], const float nhi[3], Slot &slot) {
+// `c` implies).  `cone_too`: a triangle-light leaf, a posed leaf or an inner child; `flux_scale`: the slot's scale (1 for a leaf: its flux
+// goes in as it is); `stored_cos_e`: where the cosine of omega_e stands as a libm computed it (stored_cos_e below), or null.
+RT_HD void refit_slot(const Summary &c, const bool cone_too, const float flux_scale, const float nlo[3], const float nhi[3], Slot &slot,
+                      const float *stored_cos_e = nullptr) {
     if (finite_box(c)) {
         for (int a = 0; a < 3; ++a) {
             slot.lo[a] = uint8_t(floorf(quantise(c.lo[a], nlo[a], nhi[a])));
@@ -128,7 +132,7 @@ RT_HD void refit_slot(const Summary &c, const bool cone_too, const float flux_sc
     if (cone_too) {
         slot.flux = flux_scale == 1.0f ? c.flux : c.flux * flux_scale;
         slot.axis = encode_axis(c.axis);
-        slot.cosines = encode_cosines(portable_cos(c.omega_n), max2(portable_cos(c.omega_e), 0.0f));
+        slot.cosines = encode_cosines(portable_cos(c.omega_n), max2(stored_cos_e ? *stored_cos_e : portable_cos(c.omega_e), 0.0f));
     }
 }
 
@@ -158,8 +162,18 @@ RT_HD void fold_child(Summary &acc, const bool started, const Summary &c) {
 RT_HD Summary child_summary(const uint32_t link, const Summary *leaf, const Summary *node_summary) {
     return (link & LEAF_NODE_BIT) ? leaf[link & PRIM_INDEX_BITS] : node_summary[link];
 }
-RT_HD bool slot_takes_cone(const uint32_t link, const rayhip_light *lights) {
-    return (link & LEAF_NODE_BIT) == 0 || light_type(lights[link & PRIM_INDEX_BITS]) == LIGHT_TYPE_TRI;
+// `posed`: one byte per light slot, not zero where rayhip_scene_set_lights replaced the record (light_pose.h), or null for none.  The
+// leaf of such a light takes flux, axis and cosines from its summary as a triangle light's does.
+RT_HD bool posed_leaf(const uint32_t link, const uint8_t *posed) {
+    return posed != nullptr && (link & LEAF_NODE_BIT) != 0 && posed[link & PRIM_INDEX_BITS] != 0;
+}
+RT_HD bool slot_takes_cone(const uint32_t link, const rayhip_light *lights, const uint8_t *posed = nullptr) {
+    return (link & LEAF_NODE_BIT) == 0 || light_type(lights[link & PRIM_INDEX_BITS]) == LIGHT_TYPE_TRI || posed_leaf(link, posed);
+}
+// The scene build encodes cosf(omega_e).  Every angle a summary holds is 0, PI / 2 or PI, where portable_cos gives what cosf gives,
+// but a directional light's: its cosine is taken from the record, where AddLight stored cosf(angle) (dir.cos_angle, params[3]).
+RT_HD const float *stored_cos_e(const uint32_t link, const rayhip_light *lights, const uint8_t *posed) {
+    return posed_leaf(link, posed) && light_type(lights[link & PRIM_INDEX_BITS]) == LIGHT_TYPE_DIR ? &lights[link & PRIM_INDEX_BITS].params[3] : nullptr;
 }
 
 // the scale of slot i of node w: the table's entry for an inner child, 1 for a leaf
@@ -168,9 +182,9 @@ RT_HD float slot_flux_scale(const uint32_t link, const float *slot_scale, const 
 }
 
 // node `w` as ONE thread refits it (the host driver; the device kernel spreads the same functions over eight lanes)
-// `slot_scale`: 8 per node (slot_scales), or null for 1 everywhere
+// `slot_scale`: 8 per node (slot_scales), or null for 1 everywhere; `posed`: one byte per light slot (posed_leaf), or null
 RT_HD void refit_light_node(rayhip_light_cwbvh_node *nodes, const uint32_t w, const rayhip_light *lights, const Summary *leaf, Summary *node_summary,
-                            float4 *children, const float *slot_scale) {
+                            float4 *children, const float *slot_scale, const uint8_t *posed = nullptr) {
     rayhip_light_cwbvh_node &n = nodes[w];
     Summary c[8], own;
     float nlo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, nhi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
@@ -200,7 +214,8 @@ RT_HD void refit_light_node(rayhip_light_cwbvh_node *nodes, const uint32_t w, co
         }
         Slot slot;
         slot.flux = n.flux[i], slot.axis = n.axis[i], slot.cosines = n.cos_omega_ne[i];
-        refit_slot(c[i], slot_takes_cone(n.child[i], lights), slot_flux_scale(n.child[i], slot_scale, w, i), nlo, nhi, slot);
+        refit_slot(c[i], slot_takes_cone(n.child[i], lights, posed), slot_flux_scale(n.child[i], slot_scale, w, i), nlo, nhi, slot,
+                   stored_cos_e(n.child[i], lights, posed));
         for (int a = 0; a < 3; ++a) {
             n.ch_bbox_min[a][i] = slot.lo[a], n.ch_bbox_max[a][i] = slot.hi[a];
         }
@@ -261,24 +276,25 @@ inline int plan_levels(const rayhip_light_cwbvh_node *nodes, const uint32_t n_no
 
 // box, axis and angles of a light that is NOT a triangle (it does not move with vertices), as the scene build computes them:
 // sums from the left, cross products as a*b - c*d.  The flux is not set here (leaf_table takes it from the uploaded tree).
-inline void static_light_summary(const rayhip_light &l, Summary &s) {
+// (RT_HD: the host runs it once per upload, k_pose_lights once per record a call replaces.)
+RT_HD void corner_box(const f3 *c, const int n, Summary &s) {
+    for (int a = 0; a < 3; ++a) {
+        s.lo[a] = FLT_MAX, s.hi[a] = -FLT_MAX;
+    }
+    for (int k = 0; k < n; ++k) {
+        const float v[3] = {c[k].x, c[k].y, c[k].z};
+        for (int a = 0; a < 3; ++a) {
+            s.lo[a] = min2(s.lo[a], v[a]), s.hi[a] = max2(s.hi[a], v[a]);
+        }
+    }
+}
+RT_HD void static_light_summary(const rayhip_light &l, Summary &s) {
     const float *p = l.params;
     s.flux = 0.0f;
     s.axis[0] = 0.0f, s.axis[1] = 1.0f, s.axis[2] = 0.0f;
     s.lo[0] = s.lo[1] = s.lo[2] = s.hi[0] = s.hi[1] = s.hi[2] = 0.0f;
     s.omega_n = PI, s.omega_e = PI / 2.0f;
     const uint32_t type = light_type(l);
-    auto corners = [&](const f3 *c, const int n) {
-        for (int a = 0; a < 3; ++a) {
-            s.lo[a] = FLT_MAX, s.hi[a] = -FLT_MAX;
-        }
-        for (int k = 0; k < n; ++k) {
-            const float v[3] = {c[k].x, c[k].y, c[k].z};
-            for (int a = 0; a < 3; ++a) {
-                s.lo[a] = min2(s.lo[a], v[a]), s.hi[a] = max2(s.hi[a], v[a]);
-            }
-        }
-    };
     if (type == LIGHT_TYPE_SPHERE) {
         const float r = p[7];
         for (int a = 0; a < 3; ++a) {
@@ -295,12 +311,12 @@ inline void static_light_summary(const rayhip_light &l, Summary &s) {
         u = u * p[7], v = v * p[7], dir = dir * (0.5f * p[11]);
         const f3 c[8] = {pos + dir + u + v, pos + dir + u - v, pos + dir - u + v, pos + dir - u - v,
                          pos - dir + u + v, pos - dir + u - v, pos - dir - u + v, pos - dir - u - v};
-        corners(c, 8);
+        corner_box(c, 8, s);
     } else if (type == LIGHT_TYPE_RECT || type == LIGHT_TYPE_DISK) {
         const f3 pos = f3{p[0], p[1], p[2]};
         const f3 u = f3{0.5f * p[4], 0.5f * p[5], 0.5f * p[6]}, v = f3{0.5f * p[8], 0.5f * p[9], 0.5f * p[10]};
         const f3 c[4] = {pos + u + v, pos + u - v, pos - u + v, pos - u - v};
-        corners(c, 4);
+        corner_box(c, 4, s);
         const f3 n = cross(u, v);
         const float len = sqrtf((n.x * n.x + n.y * n.y) + n.z * n.z);
         if (len > 0.0f && len <= 3.402823466e+38f) { // (a rect or disk without area keeps the axis (0, 1, 0), as a triangle without area does)
@@ -354,14 +370,14 @@ inline uint32_t refit_tri_lights_host(const rayhip_light *lights, const uint32_t
 
 // ... and the tree, level by level (0 / 1 / 2 as plan_levels).  `node_summary`: n_nodes records of scratch.
 inline int refit_light_nodes_host(rayhip_light_cwbvh_node *nodes, const uint32_t n_nodes, const rayhip_light *lights, const uint32_t n_lights,
-                                  const Summary *leaf, Summary *node_summary, float4 *children, const float *slot_scale) {
+                                  const Summary *leaf, Summary *node_summary, float4 *children, const float *slot_scale, const uint8_t *posed = nullptr) {
     std::vector<uint32_t> level_nodes, level_offset;
     const int rc = plan_levels(nodes, n_nodes, n_lights, level_nodes, level_offset);
     if (rc) {
         return rc;
     }
     for (const uint32_t w : level_nodes) { // (sorted by height: a node comes after everything below it)
-        refit_light_node(nodes, w, lights, leaf, node_summary, children, slot_scale);
+        refit_light_node(nodes, w, lights, leaf, node_summary, children, slot_scale, posed);
     }
     return 0;
 }

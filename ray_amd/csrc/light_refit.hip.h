@@ -62,13 +62,14 @@ __device__ __forceinline__ Summary load_summary(const Summary *p) {
 }
 
 // eight lanes per node of ONE height: level_nodes[0 .. n) name them, lane (g * 8 + i) of the launch has slot i of node g.
-// Reads the leaf table, the summaries of lower heights and the slot's flux scale (8 per node), writes its node, the node's summary and
-// its light_children rows.
+// Reads the leaf table, the summaries of lower heights, the slot's flux scale (8 per node) and `posed` (one byte per light slot, or
+// null: light_refit.h, posed_leaf), writes its node, the node's summary and its light_children rows.
 // Every lane of a wavefront stays in the kernel to its end (the shuffles want their partners): a group past `n` and the lane of an
 // empty slot only skip their loads and stores.
 __global__ void __launch_bounds__(256) k_refit_light_level(rayhip_light_cwbvh_node *nodes, const uint32_t *__restrict__ level_nodes, const uint32_t n,
                                                           const rayhip_light *__restrict__ lights, const Summary *__restrict__ leaf, Summary *node_summary,
-                                                          float4 *__restrict__ children, const float *__restrict__ slot_scale) {
+                                                          float4 *__restrict__ children, const float *__restrict__ slot_scale,
+                                                          const uint8_t *__restrict__ posed) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t g = t >> 3;
     const int i = int(t & 7u);
@@ -106,7 +107,7 @@ __global__ void __launch_bounds__(256) k_refit_light_level(rayhip_light_cwbvh_no
     if (used) {
         Slot slot;
         slot.flux = mine.flux[0], slot.axis = mine.axis[0], slot.cosines = mine.cos_omega_ne[0];
-        refit_slot(c, slot_takes_cone(link, lights), slot_flux_scale(link, slot_scale, w, i), nlo, nhi, slot);
+        refit_slot(c, slot_takes_cone(link, lights, posed), slot_flux_scale(link, slot_scale, w, i), nlo, nhi, slot, stored_cos_e(link, lights, posed));
         for (int a = 0; a < 3; ++a) {
             node->ch_bbox_min[a][i] = mine.ch_bbox_min[a][0] = slot.lo[a], node->ch_bbox_max[a][i] = mine.ch_bbox_max[a][0] = slot.hi[a];
         }

@@ -34,6 +34,7 @@
 #include "morph.hip.h"
 #include "normals.hip.h"
 #include "light_refit.hip.h"
+#include "light_pose.hip.h"
 #include "instances.hip.h"
 #include "scene_blob.h"
 #include "scene_rebuild.h"

@@ -183,7 +183,13 @@ struct rayhip_ctx {
         DevBuf node_summary;                // one Summary per node: scratch of the level launches
         DevBuf slot_scale;                  // 8 floats per node: stored flux over summed flux of the inner slots at the upload pose (slot_scales)
         uint32_t degenerate = 0;            // triangle lights without area the last refit met
+        bool tri_leaves = false;            // `leaf` holds the triangle lights' summaries: the tables are prepared without them
+        // ... and what rayhip_scene_set_lights checks its slots against and leaves behind (light_pose.h): per light slot whether
+        // li_indices names it, whether a call replaced its record since the tables were prepared (its leaf takes flux and cone from
+        // the leaf table from then on), and one claim word
+        DevBuf live, posed, claim;
     } light_refit;
+    DevBuf light_stage, light_args, light_counters; // rayhip_scene_set_lights: staged records, summaries and slots; the caller's arrays; the findings
     // skins (rayhip_skin_create, skin.h): rest pose and influences of a vertex range, on the device until the next scene upload
     struct Skin {
         bool live = false;
@@ -936,7 +942,8 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
     for (DevBuf *b : {&c->refit.level_nodes, &c->refit.first_entry, &c->refit.scratch, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices,
                       &c->light_refit.level_nodes, &c->light_refit.leaf, &c->light_refit.node_summary, &c->light_refit.slot_scale, &c->skin_stage,
                       &c->skin_palettes, &c->skin_counters, &c->refit.d_slot_flags, &c->refit.d_live, &c->refit.d_slot_claim, &c->instance_stage,
-                      &c->instance_args, &c->instance_counters}) {
+                      &c->instance_args, &c->instance_counters, &c->light_refit.live, &c->light_refit.posed, &c->light_refit.claim, &c->light_stage,
+                      &c->light_args, &c->light_counters}) {
         b->release();
     }
     for (hipEvent_t e : c->events) {

@@ -2,7 +2,8 @@
 // deforming a scene that is on the device.  In reading order: the tables an upload or instance update leaves behind (prepare_refit,
 // keep_light_vertices, upload_vertex_checks, upload_instance_checks, prepare_light_refit), the phase stamps, the preconditions, the light
 // refit and the geometry refit behind new vertices, the entry points (rayhip_scene_update_vertices, its _blob and _device forms; refit.h),
-// the instances that move (rayhip_scene_set_instance_transforms and its _device form; instances.h), the
+// the instances that move (rayhip_scene_set_instance_transforms and its _device form; instances.h), the analytic lights that move or
+// change colour (rayhip_scene_set_lights and its _device form; light_pose.h), the
 // skins (rayhip_skin_create / _destroy, rayhip_scene_pose_skins; skin.h), the morph sets (rayhip_morph_create / _destroy,
 // rayhip_scene_pose; morph.h), the normal sets (rayhip_normals_create / _destroy; normals.h: recomputed at the top of the geometry
 // refit) and the switch (rayhip_scene_refit_lights; light_refit.h).
@@ -143,7 +144,7 @@ static int prepare_light_refit(rayhip_ctx *c, const rayhip_scene_desc *d) {
     const rayhip_light_cwbvh_node *nodes = d->light_cwnodes;
     const uint32_t n_lights = d->lights_count, n_nodes = d->light_cwnodes_count;
     rayhip_ctx::LightRefit &lr = c->light_refit;
-    lr.ready = false;
+    lr.ready = false, lr.tri_leaves = false;
     std::vector<uint32_t> level_nodes;
     if (const int rc = rayhip_light_refit::plan_levels(nodes, n_nodes, n_lights, level_nodes, lr.level_offset)) {
         return rc == 2 ? fail("rayhip_scene_refit_lights: the light tree is higher than %u levels", rayhip_light_refit::MAX_LEVELS)
@@ -160,7 +161,14 @@ static int prepare_light_refit(rayhip_ctx *c, const rayhip_scene_desc *d) {
         lr.node_summary.alloc(size_t(n_nodes) * sizeof(rayhip_light_refit::Summary))) {
         return 1;
     }
-    HIP_TRY(hipStreamSynchronize(c->stream)); // the three vectors go out of scope
+    // ... and what rayhip_scene_set_lights checks its slots against (light_pose.h): the slots li_indices names, one claim word per slot,
+    // and the table of the lights it replaced -- none: the tree just uploaded holds the words of every leaf
+    const std::vector<uint8_t> live = rayhip_light_pose::live_table(d->li_indices, d->li_indices_count, n_lights);
+    if (upload(c, lr.live, live.data(), live.size()) || lr.posed.alloc(n_lights) || lr.claim.alloc(size_t(n_lights) * sizeof(uint32_t))) {
+        return 1;
+    }
+    HIP_TRY(hipMemsetAsync(lr.posed.p, 0, lr.posed.bytes, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the four vectors go out of scope
     lr.ready = true;
     return 0;
 }
@@ -224,6 +232,23 @@ static const uint32_t *pinned_light_vertex(const rayhip_ctx *c, const uint32_t f
 // ---- the light refit behind the geometry refit of a vertex update, in stream order (light_refit.hip.h) ------------------------------
 // the triangle lights' corners and summaries, then the tree, one launch per height.  `d_degenerate`: where the triangles without area
 // are counted.
+// the tree alone, one launch per height, lowest first: under the leaf table as it is on the device now
+static int refit_light_levels(rayhip_ctx *c) {
+    rayhip_ctx::LightRefit &lr = c->light_refit;
+    for (size_t h = 0; h + 1 < lr.level_offset.size(); ++h) {
+        const uint32_t n = lr.level_offset[h + 1] - lr.level_offset[h];
+        if (n == 0) {
+            continue;
+        }
+        rayhip_light_refit::k_refit_light_level<<<unsigned((size_t(n) * 8 + 255) / 256), 256, 0, c->stream>>>(
+            c->light_cwnodes.as<rayhip_light_cwbvh_node>(), lr.level_nodes.as<uint32_t>() + lr.level_offset[h], n, c->lights.as<rayhip_light>(),
+            lr.leaf.as<rayhip_light_refit::Summary>(), lr.node_summary.as<rayhip_light_refit::Summary>(), c->light_children.as<float4>(),
+            lr.slot_scale.as<float>(), lr.posed.as<uint8_t>());
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
 static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, const VertexStamps &st) {
     rayhip_ctx::LightRefit &lr = c->light_refit;
     if (!lr.ready) {
@@ -237,17 +262,10 @@ static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, const VertexStamp
             lr.leaf.as<rayhip_light_refit::Summary>(), d_degenerate);
         HIP_TRY(hipGetLastError());
     }
+    lr.tri_leaves = true;
     HIP_TRY(st.stamp("light corners"));
-    for (size_t h = 0; h + 1 < lr.level_offset.size(); ++h) {
-        const uint32_t n = lr.level_offset[h + 1] - lr.level_offset[h];
-        if (n == 0) {
-            continue;
-        }
-        rayhip_light_refit::k_refit_light_level<<<unsigned((size_t(n) * 8 + 255) / 256), 256, 0, s>>>(
-            c->light_cwnodes.as<rayhip_light_cwbvh_node>(), lr.level_nodes.as<uint32_t>() + lr.level_offset[h], n, c->lights.as<rayhip_light>(),
-            lr.leaf.as<rayhip_light_refit::Summary>(), lr.node_summary.as<rayhip_light_refit::Summary>(), c->light_children.as<float4>(),
-            lr.slot_scale.as<float>());
-        HIP_TRY(hipGetLastError());
+    if (refit_light_levels(c)) {
+        return 1;
     }
     HIP_TRY(st.stamp("light tree refitted"));
     return 0;
@@ -653,6 +671,131 @@ int rayhip_scene_set_instance_transforms_device(rayhip_ctx *c, uint32_t n, const
     HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
     HIP_TRY(st.stamp("begin"));
     return set_instance_transforms(c, st, n, device_slots, device_xforms);
+}
+
+// ---- analytic lights that move or change colour: records in, leaf summaries on the device, the light tree refitted (light_pose.h) ----
+// Sphere, spot, directional, line, rect and disk lights.  k_pose_lights stages the new records with their summaries and counts what is
+// wrong with the call; only when its counters came back zero are they scattered into the light array and the leaf table of the light
+// refit (k_commit_lights, which also marks the slots in `posed`), and the tree is refitted by the level launches of the vertex update:
+// boxes, quantised child boxes, flux, cones and light_children rows.  The triangle lights' corners and summaries are where the last
+// refit left them -- no record of theirs changes here, so no pass over them but the first.  The call is bound by its launches and its
+// one read-back.
+// `d_slots` / `d_records`: device memory, complete and stable until the call returns.
+static int set_lights(rayhip_ctx *c, const VertexStamps &st, const uint32_t n, const uint32_t *d_slots, const rayhip_light *d_records) {
+    namespace lp = rayhip_light_pose;
+    rayhip_ctx::LightRefit &lr = c->light_refit;
+    hipStream_t s = c->stream;
+    // one block: [n] staged records of 64 bytes, [n] summaries of 48 bytes, [n] slots
+    const size_t leaf_at = size_t(n) * 64, slots_at = leaf_at + size_t(n) * 48;
+    if (c->light_stage.alloc(slots_at + size_t(n) * 4) || c->light_counters.alloc(8 * sizeof(uint32_t))) {
+        return 1;
+    }
+    float4 *d_staged = c->light_stage.as<float4>();
+    float4 *d_staged_leaf = reinterpret_cast<float4 *>(c->light_stage.as<uint8_t>() + leaf_at);
+    uint32_t *d_staged_slots = reinterpret_cast<uint32_t *>(c->light_stage.as<uint8_t>() + slots_at);
+    uint32_t *d_counters = c->light_counters.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint32_t), s));
+    if (lr.lights_count) {
+        HIP_TRY(hipMemsetAsync(lr.claim.p, 0, size_t(lr.lights_count) * sizeof(uint32_t), s));
+    }
+    lp::k_pose_lights<<<(n + 255) / 256, 256, 0, s>>>(d_slots, d_records, n, (reinterpret_cast<uintptr_t>(d_records) & 15u) == 0u, c->lights.as<rayhip_light>(),
+                                                     lr.lights_count, lr.live.as<uint8_t>(), lr.claim.as<uint32_t>(), d_staged, d_staged_leaf, d_staged_slots,
+                                                     d_counters);
+    HIP_TRY(hipGetLastError());
+    uint32_t findings[lp::N_FINDINGS] = {};
+    HIP_TRY(hipMemcpyAsync(findings, d_counters, sizeof(findings), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(st.stamp("lights checked"));
+    if (findings[lp::BAD_SLOT] != 0) {
+        return fail("%s: %u of the slots are outside the %u light slots, or not named by li_indices", st.who, findings[lp::BAD_SLOT], lr.lights_count);
+    }
+    if (findings[lp::DUPLICATE] != 0) {
+        return fail("%s: %u slots are named more than once", st.who, findings[lp::DUPLICATE]);
+    }
+    if (findings[lp::BAD_TYPE] != 0) {
+        return fail("%s: %u of the held or new records are triangle or environment lights", st.who, findings[lp::BAD_TYPE]);
+    }
+    if (findings[lp::FLAGS_CHANGED] != 0) {
+        return fail("%s: word 0 of %u records (type and flags) differs from the one the slot holds", st.who, findings[lp::FLAGS_CHANGED]);
+    }
+    if (findings[lp::NOT_FINITE] != 0) {
+        return fail("%s: %u records have a colour or a parameter that is not finite", st.who, findings[lp::NOT_FINITE]);
+    }
+    // (the counters are back and zero: from here on the live light arrays are written)
+    lp::k_commit_lights<<<(n + 255) / 256, 256, 0, s>>>(d_staged, d_staged_leaf, d_staged_slots, n, c->lights.as<rayhip_light>(),
+                                                       lr.leaf.as<rayhip_light_refit::Summary>(), lr.posed.as<uint8_t>(), lr.lights_count);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(st.stamp("lights committed"));
+    // the level launches read the summary of EVERY leaf.  Those of the triangle lights are written by the first pass over them, not when
+    // the tables are prepared: where none ran yet it runs here (corners and summaries of the pose that is on the device, the bytes a
+    // vertex update would write); afterwards no record of theirs changes in this call, and the tree alone is refitted
+    if (!lr.tri_leaves) {
+        if (refit_lights(c, d_counters + lp::N_FINDINGS, st)) {
+            return 1;
+        }
+        HIP_TRY(hipMemcpyAsync(&lr.degenerate, d_counters + lp::N_FINDINGS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    } else if (refit_light_levels(c)) {
+        return 1;
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(st.stamp("light tree refitted"));
+    return 0;
+}
+
+// what both forms check before anything else: 0 = go on, 1 / 2 = the return code
+static int light_move_possible(rayhip_ctx *c, const char *who, const uint32_t n, const void *slots, const void *records) {
+    if (n > 0 && (!slots || !records)) {
+        return fail("%s: a null pointer", who);
+    }
+    if (!c->have_scene) {
+        (void)fail("%s before rayhip_scene_upload", who);
+        return 2;
+    }
+    if (!c->light_refit.on || !c->light_refit.ready) {
+        (void)fail("%s: rayhip_scene_refit_lights is off, or its tables are not prepared; the switch keeps the light tree refittable", who);
+        return 2;
+    }
+    return 0;
+}
+
+int rayhip_scene_set_lights(rayhip_ctx *c, uint32_t n, const uint32_t *slots, const rayhip_light *records) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (const int rc = light_move_possible(c, "rayhip_scene_set_lights", n, slots, records)) {
+        return rc;
+    }
+    if (n == 0) {
+        return 0;
+    }
+    const VertexStamps st{c, "rayhip_scene_set_lights"};
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    // the caller's arrays onto the device: [n] records, [n] slots
+    if (c->light_args.alloc(size_t(n) * 68)) {
+        return 1;
+    }
+    rayhip_light *d_records = c->light_args.as<rayhip_light>();
+    uint32_t *d_slots = reinterpret_cast<uint32_t *>(c->light_args.as<uint8_t>() + size_t(n) * 64);
+    HIP_TRY(hipMemcpyAsync(d_records, records, size_t(n) * 64, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_slots, slots, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
+    return set_lights(c, st, n, d_slots, d_records); // (it waits for the stream before it returns: the arrays may go away)
+}
+
+int rayhip_scene_set_lights_device(rayhip_ctx *c, uint32_t n, const uint32_t *device_slots, const rayhip_light *device_records) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (const int rc = light_move_possible(c, "rayhip_scene_set_lights_device", n, device_slots, device_records)) {
+        return rc;
+    }
+    if (n == 0) {
+        return 0;
+    }
+    const VertexStamps st{c, "rayhip_scene_set_lights_device"};
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    return set_lights(c, st, n, device_slots, device_records);
 }
 
 // ---- the skins ---------------------------------------------------------------------------------------------------------------------------

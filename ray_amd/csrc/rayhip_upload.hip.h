@@ -879,6 +879,13 @@ int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_byt
         src = c->light_tri_geom.p, bytes = size_t(c->light_refit.lights_count) * 4 * sizeof(float4);
     } else if (which == 8) {
         src = c->mesh_instances.p, bytes = size_t(c->instances_count) * sizeof(rayhip_mesh_instance);
+    } else if (which == 9) {
+        src = c->lights.p, bytes = size_t(c->light_refit.lights_count) * sizeof(rayhip_light);
+    } else if (which == 10) { // (the leaf table exists once the light refit is prepared)
+        if (!c->light_refit.ready) {
+            return fail("rayhip_k_read_accel: array 10 needs rayhip_scene_refit_lights");
+        }
+        src = c->light_refit.leaf.p, bytes = size_t(c->light_refit.lights_count) * sizeof(rayhip_light_refit::Summary);
     } else {
         return fail("rayhip_k_read_accel: no array %d", which);
     }
