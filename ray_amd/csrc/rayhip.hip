@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cmath>
 #include <chrono>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>

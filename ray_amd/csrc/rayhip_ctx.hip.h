@@ -147,7 +147,7 @@ struct rayhip_ctx {
     struct { uint32_t vertices, vtx_indices, tri_materials, materials; } geometry = {};
     uint32_t instances_count = 0; // mesh instances on the device (scene_upload and scene_update set it)
     // ---- deforming the scene that is on the device (rayhip_deform.hip.h): the tables an upload or instance update leaves for a vertex
-    // update, the same for the light refit behind it, and the skins.  rayhip_ctx_destroy releases what lies here in one list.
+    // update, the same for the light refit behind it, and the handles over vertex ranges.  rayhip_ctx_destroy releases what lies here in one list.
     // what rayhip_scene_update_vertices needs of the last full upload / instance update (refit.h)
     struct Refit {
         DevBuf level_nodes;                 // bottom-level BVH2 nodes sorted by height ...
@@ -190,69 +190,116 @@ struct rayhip_ctx {
         DevBuf live, posed, claim;
     } light_refit;
     DevBuf light_stage, light_args, light_counters; // rayhip_scene_set_lights: staged records, summaries and slots; the caller's arrays; the findings
-    // skins (rayhip_skin_create, skin.h): rest pose and influences of a vertex range, on the device until the next scene upload
-    struct Skin {
+    // ---- handles over vertex ranges: skins, morph sets and normal sets.  A record of any kind begins with the same head ...
+    struct RangeHead {
         bool live = false;
-        int id = 0; // the handle the caller holds: (serial << 4) | slot, so a handle of a discarded skin never names a later one
-        uint32_t first = 0, count = 0, bones_count = 0;
-        DevBuf rest, indices, weights; // rayhip_vertex [count], uint16 [count][4], float [count][4]
-    } skins[rayhip_skin::MAX_SKINS];
-    uint32_t skin_serial = 0;
-    // the live skin handle `id` names, or null
-    Skin *skin_of(const int id) {
-        Skin &k = skins[id & int(rayhip_skin::MAX_SKINS - 1)];
-        return id > 0 && k.live && k.id == id ? &k : nullptr;
-    }
-    void discard_skins() {
-        for (Skin &k : skins) {
-            k.live = false;
-            k.rest.release(), k.indices.release(), k.weights.release();
+        int id = 0; // the handle the caller holds: (serial << 4) | slot, so a handle of a discarded record never names a later one
+        uint32_t first = 0, count = 0; // vertices [first, first + count) of the scene
+        bool meets(const uint32_t f, const uint32_t n) const { return f < first + count && first < f + n; }
+        bool covers(const uint32_t v) const { return v >= first && v - first < count; }
+    };
+    // ... and lives in a table of N slots (16 of every kind: the low four bits of a handle) with the serial of the handles issued so far.
+    // T: a RangeHead with what the kind keeps on the device, and release(), which frees that and ends the record's life.
+    template <typename T, uint32_t N> struct RangeTable {
+        static_assert(N == 16, "a handle holds its slot in four bits");
+        static constexpr uint32_t SLOTS = N;
+        const char *const noun; // what the error texts call a record: "skin", "morph set", "normal set"
+        T slots[N];
+        uint32_t serial = 0;
+        explicit RangeTable(const char *what) : noun(what) {}
+        T *begin() { return slots; }
+        T *end() { return slots + N; }
+        const T *begin() const { return slots; }
+        const T *end() const { return slots + N; }
+        // the live record handle `id` names, or null
+        T *of(const int id) {
+            T &r = slots[id & int(N - 1)];
+            return id > 0 && r.live && r.id == id ? &r : nullptr;
         }
-    }
+        // where a record over [first, first + count) goes: `slot` is the lowest free one.  Refused (1, in the name of `who`) where a live
+        // record meets the range -- the one in the highest such slot is named -- or, failing that, where every slot is live
+        int free_slot(const char *who, const uint32_t first, const uint32_t count, int &slot) const {
+            slot = -1;
+            for (int k = int(N) - 1; k >= 0; --k) {
+                if (!slots[k].live) {
+                    slot = k;
+                } else if (slots[k].meets(first, count)) {
+                    return fail("%s: vertices [%u, %u + %u) overlap %s %d", who, first, first, count, noun, slots[k].id);
+                }
+            }
+            return slot < 0 ? fail("%s: %u %ss are live already", who, N, noun) : 0;
+        }
+        // the record in `slot` comes to life over [first, first + count); its handle
+        int issue(const int slot, const uint32_t first, const uint32_t count) {
+            serial = (serial % 0x7ffffffu) + 1; // (1 .. 2^27 - 1: the handle stays a positive int, and is never a return code)
+            T &r = slots[slot];
+            r.live = true, r.id = int(serial << 4) | slot, r.first = first, r.count = count;
+            return r.id;
+        }
+        // the record handle `id` names ends its life once the stream is idle; 2 = the handle names none (in the name of `who`)
+        int destroy(hipStream_t stream, const char *who, const int id) {
+            T *r = of(id);
+            if (!r) {
+                (void)fail("%s: %s %d is not live", who, noun, id);
+                return 2;
+            }
+            HIP_TRY(hipStreamSynchronize(stream));
+            r->release();
+            return 0;
+        }
+        void discard() {
+            for (T &r : slots) {
+                r.release();
+            }
+        }
+    };
+    // skins (rayhip_skin_create, skin.h): rest pose and influences of a vertex range, on the device until the next scene upload
+    struct Skin : RangeHead {
+        uint32_t bones_count = 0;
+        DevBuf rest, indices, weights; // rayhip_vertex [count], uint16 [count][4], float [count][4]
+        void release() {
+            live = false;
+            rest.release(), indices.release(), weights.release();
+        }
+    };
+    RangeTable<Skin, rayhip_skin::MAX_SKINS> skins{"skin"};
     // morph sets (rayhip_morph_create, morph.h): base records and the row table of the targets' deltas of a vertex range, on the device
     // until the next scene upload
-    struct Morph {
-        bool live = false;
-        int id = 0; // the handle the caller holds, made as a skin's
-        uint32_t first = 0, count = 0, targets_count = 0;
+    struct Morph : RangeHead {
+        uint32_t targets_count = 0;
         DevBuf base, row, entries; // rayhip_vertex [count], uint32 [count + 1], rayhip_morph::Entry [row[count]]
-    } morphs[rayhip_morph::MAX_MORPHS];
-    uint32_t morph_serial = 0;
-    // the live morph set handle `id` names, or null
-    Morph *morph_of(const int id) {
-        Morph &m = morphs[id & int(rayhip_morph::MAX_MORPHS - 1)];
-        return id > 0 && m.live && m.id == id ? &m : nullptr;
-    }
-    void discard_morphs() {
-        for (Morph &m : morphs) {
-            m.live = false;
-            m.base.release(), m.row.release(), m.entries.release();
+        void release() {
+            live = false;
+            base.release(), row.release(), entries.release();
         }
-    }
+    };
+    RangeTable<Morph, rayhip_morph::MAX_MORPHS> morphs{"morph set"};
     // normal sets (rayhip_normals_create, normals.h): the faces of a vertex range and its row tables, on the device until the next scene
     // upload; every call that writes the vertex array recomputes n and / or b of the range behind its copy (recompute_normal_sets)
-    struct Normals {
-        bool live = false;
-        int id = 0; // the handle the caller holds, made as a skin's
-        uint32_t first = 0, count = 0, flags = 0, faces_count = 0;
+    struct Normals : RangeHead {
+        uint32_t flags = 0, faces_count = 0;
         bool welded = false;
         DevBuf faces, row, entries, wrow, wentries; // uint32 [faces_count], [count + 1], [row[count]]; of a welded set [count + 1], [wrow[count]]
         DevBuf frames;                              // rayhip_normals::FaceFrame [faces_count]: scratch of the two kernels
-    } normal_sets[rayhip_normals::MAX_SETS];
-    uint32_t normals_serial = 0;
-    // the live normal set handle `id` names, or null
-    Normals *normals_of(const int id) {
-        Normals &n = normal_sets[id & int(rayhip_normals::MAX_SETS - 1)];
-        return id > 0 && n.live && n.id == id ? &n : nullptr;
-    }
-    static void release_normals(Normals &n) {
-        n.live = false;
-        n.faces.release(), n.row.release(), n.entries.release(), n.wrow.release(), n.wentries.release(), n.frames.release();
-    }
-    void discard_normals() {
-        for (Normals &n : normal_sets) {
-            release_normals(n);
+        void release() {
+            live = false;
+            faces.release(), row.release(), entries.release(), wrow.release(), wentries.release(), frames.release();
         }
+    };
+    RangeTable<Normals, rayhip_normals::MAX_SETS> normal_sets{"normal set"};
+    // every record of the three tables with the noun of its kind: skins, morph sets, normal sets, in this order
+    std::vector<std::pair<const RangeHead *, const char *>> vertex_ranges() const {
+        std::vector<std::pair<const RangeHead *, const char *>> out;
+        for (const Skin &k : skins) {
+            out.emplace_back(&k, skins.noun);
+        }
+        for (const Morph &m : morphs) {
+            out.emplace_back(&m, morphs.noun);
+        }
+        for (const Normals &n : normal_sets) {
+            out.emplace_back(&n, normal_sets.noun);
+        }
+        return out;
     }
     DevBuf skin_stage;    // the posed vertices of one rayhip_scene_pose[_skins] call, range after range (sized to the largest call seen)
     DevBuf skin_palettes; // ... and its palettes and morph weights
@@ -936,9 +983,9 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
         }
     }
     c->stack_spill2.release();
-    c->discard_skins();
-    c->discard_morphs();
-    c->discard_normals();
+    c->skins.discard();
+    c->morphs.discard();
+    c->normal_sets.discard();
     for (DevBuf *b : {&c->refit.level_nodes, &c->refit.first_entry, &c->refit.scratch, &c->refit.d_vertex_used, &c->refit.d_light_index, &c->refit.d_light_vertices,
                       &c->light_refit.level_nodes, &c->light_refit.leaf, &c->light_refit.node_summary, &c->light_refit.slot_scale, &c->skin_stage,
                       &c->skin_palettes, &c->skin_counters, &c->refit.d_slot_flags, &c->refit.d_live, &c->refit.d_slot_claim, &c->instance_stage,

@@ -1,12 +1,17 @@
 // rayhip_deform.hip.h -- part of librayhip's host side (one translation unit: included by rayhip.hip before rayhip_upload.hip.h):
-// deforming a scene that is on the device.  In reading order: the tables an upload or instance update leaves behind (prepare_refit,
-// keep_light_vertices, upload_vertex_checks, upload_instance_checks, prepare_light_refit), the phase stamps, the preconditions, the light
-// refit and the geometry refit behind new vertices, the entry points (rayhip_scene_update_vertices, its _blob and _device forms; refit.h),
-// the instances that move (rayhip_scene_set_instance_transforms and its _device form; instances.h), the analytic lights that move or
-// change colour (rayhip_scene_set_lights and its _device form; light_pose.h), the
-// skins (rayhip_skin_create / _destroy, rayhip_scene_pose_skins; skin.h), the morph sets (rayhip_morph_create / _destroy,
-// rayhip_scene_pose; morph.h), the normal sets (rayhip_normals_create / _destroy; normals.h: recomputed at the top of the geometry
-// refit) and the switch (rayhip_scene_refit_lights; light_refit.h).
+// deforming a scene that is on the device.  In reading order:
+//   - the tables an upload or instance update leaves behind (prepare_refit, keep_light_vertices, upload_vertex_checks,
+//     upload_instance_checks, prepare_light_refit);
+//   - what the entry points share: the phase stamps, the preconditions, the launch grid, the read-back;
+//   - the light refit and the geometry refit behind new vertices, and the top level behind either;
+//   - the vertex updates (rayhip_scene_update_vertices, its _blob and _device forms; refit.h);
+//   - the calls that take slots and records, each from host or device memory: the instances that move
+//     (rayhip_scene_set_instance_transforms[_device]; instances.h) and the analytic lights that move or change colour
+//     (rayhip_scene_set_lights[_device]; light_pose.h);
+//   - the handles over vertex ranges: skins (rayhip_skin_create / _destroy; skin.h), morph sets (rayhip_morph_create / _destroy;
+//     morph.h) and normal sets (rayhip_normals_create / _destroy; normals.h: recomputed at the top of the geometry refit);
+//   - the poses (rayhip_scene_pose, and rayhip_scene_pose_skins, which is the same without morph sets);
+//   - the switch (rayhip_scene_refit_lights; light_refit.h).
 #pragma once
 
 // what the refit needs of the upload's half of the launcher (rayhip_upload.hip.h)
@@ -66,23 +71,29 @@ static int prepare_refit(rayhip_ctx *c, const rayhip_bvh2_node *nodes, const uin
     return 0;
 }
 
+// f(light) for every triangle light that li_indices names: params[0] is its triangle, params[1] its instance slot, both as bits
+static void for_each_triangle_light(const rayhip_scene_desc *d, const std::function<void(const rayhip_light &)> &f) {
+    for (uint32_t k = 0; k < d->li_indices_count; ++k) {
+        const uint32_t i = d->li_indices[k];
+        if (i < d->lights_count && light_type(d->lights[i]) == LIGHT_TYPE_TRI) {
+            f(d->lights[i]);
+        }
+    }
+}
+
 // the vertices some triangle light's triangle uses, as they are on the device: the light arrays are not rebuilt by a vertex update,
 // so it refuses to move one of these
 static void keep_light_vertices(rayhip_ctx *c, const rayhip_scene_desc *d) {
     std::vector<std::pair<uint32_t, rayhip_vertex>> &kept = c->refit.light_vertices;
     kept.clear();
-    for (uint32_t k = 0; k < d->li_indices_count; ++k) {
-        const uint32_t i = d->li_indices[k];
-        if (i >= d->lights_count || light_type(d->lights[i]) != LIGHT_TYPE_TRI) {
-            continue;
-        }
-        const size_t tri = float_as_uint(d->lights[i].params[0]);
+    for_each_triangle_light(d, [&](const rayhip_light &l) {
+        const size_t tri = float_as_uint(l.params[0]);
         for (size_t j = tri * 3; j < tri * 3 + 3 && j < d->vtx_indices_count; ++j) {
             if (d->vtx_indices[j] < d->vertices_count) {
                 kept.emplace_back(d->vtx_indices[j], d->vertices[d->vtx_indices[j]]);
             }
         }
-    }
+    });
     std::sort(kept.begin(), kept.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
     kept.erase(std::unique(kept.begin(), kept.end(), [](const auto &x, const auto &y) { return x.first == y.first; }), kept.end());
 }
@@ -116,16 +127,12 @@ static int upload_instance_checks(rayhip_ctx *c, const rayhip_scene_desc *d) {
             r.slot_flags[mi] |= uint8_t(rayhip_instances::SLOT_LIVE);
         }
     }
-    for (uint32_t k = 0; k < d->li_indices_count; ++k) {
-        const uint32_t i = d->li_indices[k];
-        if (i >= d->lights_count || light_type(d->lights[i]) != LIGHT_TYPE_TRI) {
-            continue;
-        }
-        const uint32_t mi = float_as_uint(d->lights[i].params[1]);
+    for_each_triangle_light(d, [&](const rayhip_light &l) {
+        const uint32_t mi = float_as_uint(l.params[1]);
         if (mi < r.slot_flags.size()) {
             r.slot_flags[mi] |= uint8_t(rayhip_instances::SLOT_TRI_LIGHTS);
         }
-    }
+    });
     if (upload(c, r.d_slot_flags, r.slot_flags.data(), r.slot_flags.size()) || upload(c, r.d_live, r.live.data(), r.live.size() * sizeof(uint32_t)) ||
         r.d_slot_claim.alloc(r.slot_flags.size() * sizeof(uint32_t)) || hipStreamSynchronize(c->stream) != hipSuccess) {
         r.slot_flags.clear(); // (no table on the device: a call that moves instances says that it needs an upload)
@@ -189,16 +196,36 @@ struct VertexStamps {
     }
 };
 
-// ---- the preconditions every entry point shares ------------------------------------------------------------------------------------------
-// 0 = the context can take a vertex update, 2 = it needs rayhip_scene_upload
-static int vertex_update_possible(rayhip_ctx *c, const char *who) {
+// ---- what the entry points share: the preconditions, the launch grid, the read-back -------------------------------------------------------
+// blocks of 256 lanes over n items
+static unsigned blocks_of(const size_t n) { return unsigned((n + 255) / 256); }
+
+// `bytes` of a device buffer onto the host, now
+static bool read_back(void *dst, const DevBuf &src, const size_t bytes) {
+    return bytes == 0 || hipMemcpy(dst, src.p, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// the refusals of every call that changes the scene on the device: a pointer the caller had to give and did not (`null_pointer`), no
+// scene, and -- of the calls that rebuild a tree (`builds_trees`) -- the 8-wide form.  0 = go on, 1 / 2 = the return code
+static int scene_change_possible(rayhip_ctx *c, const char *who, const bool null_pointer, const bool builds_trees) {
+    if (null_pointer) {
+        return fail("%s: a null pointer", who);
+    }
     if (!c->have_scene) {
         (void)fail("%s before rayhip_scene_upload", who);
         return 2;
     }
-    if (c->wide == 8) {
+    if (builds_trees && c->wide == 8) {
         (void)fail("%s: the context walks the 8-wide tree, whose builder runs on the host only", who);
         return 2;
+    }
+    return 0;
+}
+
+// 0 = the context can take a vertex update, 2 = it needs rayhip_scene_upload
+static int vertex_update_possible(rayhip_ctx *c, const char *who) {
+    if (const int rc = scene_change_possible(c, who, false, true)) {
+        return rc;
     }
     // (vertex_used: prepare_refit assigns one flag per vertex, so after a successful upload the sizes agree; only an upload that
     // failed after it, over a scene that was there, leaves them apart -- and the checks below index the flags by the scene's count)
@@ -229,9 +256,7 @@ static const uint32_t *pinned_light_vertex(const rayhip_ctx *c, const uint32_t f
     return nullptr;
 }
 
-// ---- the light refit behind the geometry refit of a vertex update, in stream order (light_refit.hip.h) ------------------------------
-// the triangle lights' corners and summaries, then the tree, one launch per height.  `d_degenerate`: where the triangles without area
-// are counted.
+// ---- the light refit, in stream order behind whatever moved the lights (light_refit.hip.h) ------------------------------------------------
 // the tree alone, one launch per height, lowest first: under the leaf table as it is on the device now
 static int refit_light_levels(rayhip_ctx *c) {
     rayhip_ctx::LightRefit &lr = c->light_refit;
@@ -240,7 +265,7 @@ static int refit_light_levels(rayhip_ctx *c) {
         if (n == 0) {
             continue;
         }
-        rayhip_light_refit::k_refit_light_level<<<unsigned((size_t(n) * 8 + 255) / 256), 256, 0, c->stream>>>(
+        rayhip_light_refit::k_refit_light_level<<<blocks_of(size_t(n) * 8), 256, 0, c->stream>>>(
             c->light_cwnodes.as<rayhip_light_cwbvh_node>(), lr.level_nodes.as<uint32_t>() + lr.level_offset[h], n, c->lights.as<rayhip_light>(),
             lr.leaf.as<rayhip_light_refit::Summary>(), lr.node_summary.as<rayhip_light_refit::Summary>(), c->light_children.as<float4>(),
             lr.slot_scale.as<float>(), lr.posed.as<uint8_t>());
@@ -249,6 +274,8 @@ static int refit_light_levels(rayhip_ctx *c) {
     return 0;
 }
 
+// the whole of it: the triangle lights' corners and summaries from the vertices and instances that are on the device now, then the tree.
+// `d_degenerate`: where the triangle lights without area are counted (device memory, zeroed by the caller)
 static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, const VertexStamps &st) {
     rayhip_ctx::LightRefit &lr = c->light_refit;
     if (!lr.ready) {
@@ -256,7 +283,7 @@ static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, const VertexStamp
     }
     hipStream_t s = c->stream;
     if (lr.li_count) {
-        rayhip_light_refit::k_refit_tri_lights<<<(lr.li_count + 255) / 256, 256, 0, s>>>(
+        rayhip_light_refit::k_refit_tri_lights<<<blocks_of(lr.li_count), 256, 0, s>>>(
             c->lights.as<rayhip_light>(), lr.lights_count, c->li_indices.as<uint32_t>(), lr.li_count, c->mesh_instances.as<rayhip_mesh_instance>(), c->instances_count,
             c->vtx_indices.as<uint32_t>(), c->geometry.vtx_indices, c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->light_tri_geom.as<float4>(),
             lr.leaf.as<rayhip_light_refit::Summary>(), d_degenerate);
@@ -268,6 +295,20 @@ static int refit_lights(rayhip_ctx *c, uint32_t *d_degenerate, const VertexStamp
         return 1;
     }
     HIP_TRY(st.stamp("light tree refitted"));
+    return 0;
+}
+
+// ---- the top level behind new instance boxes: what a vertex update and a call that moves instances end with ------------------------------
+// `up`: the live slots and their boxes (and, of a vertex update, the instance array and the 4-wide roots).  The arrays under the top
+// level are the new ones already, so a plan that "needs an upload" (2) is an error here.  The line names `st.who`.
+static int rebuild_top_level_behind(rayhip_ctx *c, const rayhip_update::Plan &up, const VertexStamps &st) {
+    uint32_t tlas_root = 0xffffffffu;
+    rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
+    if (const int rc = rebuild_top_level(c, up, tlas_root, root_box)) {
+        return rc == 2 ? fail("%s: %s", st.who, std::string(g_err).c_str()) : rc;
+    }
+    refresh_top_level_view(c, tlas_root, root_box, uint32_t(up.live.size()));
+    HIP_TRY(st.stamp("top level built"));
     return 0;
 }
 
@@ -291,11 +332,11 @@ static int recompute_normal_sets(rayhip_ctx *c, const VertexStamps &st) {
         if (n.faces_count == 0) {
             continue; // (no tree reaches a triangle of the range: every record stays)
         }
-        rayhip_normals::k_face_frames<<<(n.faces_count + 255) / 256, 256, 0, c->stream>>>(c->vertices.as<rayhip_vertex>(), c->vtx_indices.as<uint32_t>(),
-                                                                                         n.faces.as<uint32_t>(), n.faces_count,
-                                                                                         n.frames.as<rayhip_normals::FaceFrame>());
+        rayhip_normals::k_face_frames<<<blocks_of(n.faces_count), 256, 0, c->stream>>>(c->vertices.as<rayhip_vertex>(), c->vtx_indices.as<uint32_t>(),
+                                                                                       n.faces.as<uint32_t>(), n.faces_count,
+                                                                                       n.frames.as<rayhip_normals::FaceFrame>());
         HIP_TRY(hipGetLastError());
-        rayhip_normals::k_vertex_frames<<<(n.count + 255) / 256, 256, 0, c->stream>>>(
+        rayhip_normals::k_vertex_frames<<<blocks_of(n.count), 256, 0, c->stream>>>(
             c->vertices.as<rayhip_vertex>() + n.first, n.row.as<uint32_t>(), n.entries.as<uint32_t>(), n.welded ? n.wrow.as<uint32_t>() : nullptr,
             n.welded ? n.wentries.as<uint32_t>() : nullptr, n.frames.as<rayhip_normals::FaceFrame>(), n.count, n.flags);
         HIP_TRY(hipGetLastError());
@@ -320,23 +361,23 @@ static int refit_after_vertices(rayhip_ctx *c, VertexStamps st) {
     uint32_t *d_degenerate = r.scratch.as<uint32_t>();
     HIP_TRY(hipMemsetAsync(d_degenerate, 0, 2 * sizeof(uint32_t), s)); // ([1]: triangle LIGHTS without area, when the lights are refitted)
     if (r.entries) {
-        rayhip_refit::k_refit_tris<<<(r.entries + 255) / 256, 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(),
-                                                                           n_tris, c->tri_indices.as<uint32_t>(), r.first_entry.as<uint32_t>(), r.entries,
-                                                                           c->tris.as<float4>(), c->tri_pitch, d_degenerate);
+        rayhip_refit::k_refit_tris<<<blocks_of(r.entries), 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(),
+                                                                        n_tris, c->tri_indices.as<uint32_t>(), r.first_entry.as<uint32_t>(), r.entries,
+                                                                        c->tris.as<float4>(), c->tri_pitch, d_degenerate);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(st.stamp("triangle records"));
     for (size_t h = 1; h < r.level_offset.size(); ++h) {
         const uint32_t n = r.level_offset[h] - r.level_offset[h - 1];
-        rayhip_refit::k_refit_level<<<(n + 255) / 256, 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), r.level_nodes.as<uint32_t>() + r.level_offset[h - 1], n,
-                                                                    c->tri_indices.as<uint32_t>(), c->vtx_indices.as<uint32_t>(), c->vertices.as<rayhip_vertex>());
+        rayhip_refit::k_refit_level<<<blocks_of(n), 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), r.level_nodes.as<uint32_t>() + r.level_offset[h - 1], n,
+                                                                 c->tri_indices.as<uint32_t>(), c->vtx_indices.as<uint32_t>(), c->vertices.as<rayhip_vertex>());
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(st.stamp("boxes refitted"));
     if (n_tris) {
-        k_fill_tri_verts<<<(n_tris + 255) / 256, 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(), n_tris,
-                                                              c->tri_materials.as<rayhip_tri_mat_data>(), c->geometry.tri_materials, c->tri_verts.as<float4>(),
-                                                              c->tri_bitangents.as<float4>());
+        k_fill_tri_verts<<<blocks_of(n_tris), 256, 0, s>>>(c->vertices.as<rayhip_vertex>(), c->geometry.vertices, c->vtx_indices.as<uint32_t>(), n_tris,
+                                                           c->tri_materials.as<rayhip_tri_mat_data>(), c->geometry.tri_materials, c->tri_verts.as<float4>(),
+                                                           c->tri_bitangents.as<float4>());
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(st.stamp("tri_verts done"));
@@ -353,8 +394,8 @@ static int refit_after_vertices(rayhip_ctx *c, VertexStamps st) {
         rayhip_bvh2_node *d_roots = reinterpret_cast<rayhip_bvh2_node *>(r.scratch.as<uint8_t>() + 256 + ((r.roots.size() * sizeof(uint32_t) + 63) & ~size_t(63)));
         if (!r.roots.empty()) {
             HIP_TRY(hipMemcpyAsync(d_which, r.roots.data(), r.roots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            rayhip_refit::k_gather_nodes<<<unsigned((r.roots.size() + 255) / 256), 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), d_which, uint32_t(r.roots.size()),
-                                                                                               d_roots);
+            rayhip_refit::k_gather_nodes<<<blocks_of(r.roots.size()), 256, 0, s>>>(c->nodes.as<rayhip_bvh2_node>(), d_which, uint32_t(r.roots.size()),
+                                                                                   d_roots);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(root_nodes.data(), d_roots, r.roots.size() * sizeof(rayhip_bvh2_node), hipMemcpyDeviceToHost, s));
         }
@@ -411,14 +452,7 @@ static int refit_after_vertices(rayhip_ctx *c, VertexStamps st) {
         }
         HIP_TRY(hipStreamSynchronize(s));
     }
-    uint32_t tlas_root = 0xffffffffu;
-    rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
-    if (const int rc = rebuild_top_level(c, up, tlas_root, root_box)) {
-        return rc == 2 ? fail("rayhip_scene_update_vertices: %s", g_err.c_str()) : rc; // (the arrays are the new ones already: an error)
-    }
-    refresh_top_level_view(c, tlas_root, root_box, uint32_t(up.live.size()));
-    HIP_TRY(st.stamp("top level built"));
-    return 0;
+    return rebuild_top_level_behind(c, up, st);
 }
 
 // ---- the entry points ----------------------------------------------------------------------------------------------------------------------
@@ -469,11 +503,13 @@ int rayhip_scene_update_vertices_blob(rayhip_ctx *c, const void *blob, size_t si
     return rayhip_scene_update_vertices(c, 0, d.vertices_count, d.vertices);
 }
 
-// ---- vertex updates whose vertices never pass through the host: arrays the caller holds on the device, and skins ------------------
-// Both run a kernel over the new vertices BEFORE the vertex array is written (checked where the caller has them / posed into a staging
-// array), read its counters back, and only then copy device to device and refit: a refused update has touched nothing.  skin.h,
-// skin.hip.h.  (The two flows are kept apart: they share the order of their steps but no step -- one kernel or one per skin, one
-// counter judged or two, one copy or one per skin -- so a common helper would take each step as a callback and shorten neither.)
+// ---- vertex updates whose vertices never pass through the host: arrays the caller holds on the device, and poses --------------------
+// Both run kernels over the new vertices BEFORE the vertex array is written (checked where the caller has them / posed into a staging
+// array), read the counters back, and only then copy device to device and refit: a refused update has touched nothing.  skin.h,
+// skin.hip.h.  The two flows share that order and the refit (refit_after_vertices), and nothing between: one kernel here and one per
+// segment of a pose, two counters judged or one, one copy or one per range.  What the flows further down do share step for step is
+// written once: the two forms of a slots-and-records call (set_records), the three kinds of handle (RangeTable in rayhip_ctx.hip.h and
+// the helpers above rayhip_skin_create), the two poses (pose_ranges) and the top level behind new boxes (rebuild_top_level_behind).
 int rayhip_scene_update_vertices_device(rayhip_ctx *c, uint32_t first_vertex, uint32_t count, const rayhip_vertex *device_vertices) {
     if (!c || use_device(c)) {
         return 1;
@@ -497,9 +533,9 @@ int rayhip_scene_update_vertices_device(rayhip_ctx *c, uint32_t first_vertex, ui
     const uint32_t n_lights = c->light_refit.on ? 0u : uint32_t(r.light_vertices.size()); // (refitted lights may move: nothing to compare)
     if (count) {
         HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
-        rayhip_skin::k_check_vertices<<<(std::max(count, n_lights) + 255) / 256, 256, 0, s>>>(device_vertices, first_vertex, count, r.d_vertex_used.as<uint8_t>(),
-                                                                                             r.d_light_index.as<uint32_t>(), r.d_light_vertices.as<rayhip_vertex>(),
-                                                                                             n_lights, d_counters);
+        rayhip_skin::k_check_vertices<<<blocks_of(std::max(count, n_lights)), 256, 0, s>>>(device_vertices, first_vertex, count, r.d_vertex_used.as<uint8_t>(),
+                                                                                           r.d_light_index.as<uint32_t>(), r.d_light_vertices.as<rayhip_vertex>(),
+                                                                                           n_lights, d_counters);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -518,6 +554,41 @@ int rayhip_scene_update_vertices_device(rayhip_ctx *c, uint32_t first_vertex, ui
     }
     HIP_TRY(st.stamp("vertices copied"));
     return refit_after_vertices(c, st);
+}
+
+// ---- calls that take slots and records: n slots of an array on the device and n records of 64 bytes for them --------------------------
+// What the host and the device form of such a call do around its body.  `possible`: the preconditions, asked first; an empty call that
+// passes them returns 0 with nothing touched.  `host_args`: the context's buffer that takes a copy of the caller's HOST arrays, [n]
+// records then [n] slots; null: `slots` and `records` are device memory, complete and stable until the call returns, and go to the
+// body as they are.  (The body waits for the stream before it returns: host arrays may go away then.)
+extern "C++" template <typename Record>
+static int set_records(rayhip_ctx *c, const char *who, const uint32_t n, const uint32_t *slots, const Record *records, DevBuf rayhip_ctx::*host_args,
+                       int (*possible)(rayhip_ctx *, const char *, uint32_t, const void *, const void *),
+                       int (*body)(rayhip_ctx *, const VertexStamps &, uint32_t, const uint32_t *, const Record *)) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (const int rc = possible(c, who, n, slots, records)) {
+        return rc;
+    }
+    if (n == 0) {
+        return 0;
+    }
+    const VertexStamps st{c, who};
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    if (!host_args) {
+        return body(c, st, n, slots, records);
+    }
+    DevBuf &args = c->*host_args;
+    if (args.alloc(size_t(n) * 68)) {
+        return 1;
+    }
+    Record *d_records = args.as<Record>();
+    uint32_t *d_slots = reinterpret_cast<uint32_t *>(args.as<uint8_t>() + size_t(n) * 64);
+    HIP_TRY(hipMemcpyAsync(d_records, records, size_t(n) * 64, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_slots, slots, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
+    return body(c, st, n, d_slots, d_records);
 }
 
 // ---- moving instances: transforms in, inverses and world boxes on the device, the top level rebuilt (instances.h, instances.hip.h) ----
@@ -547,9 +618,9 @@ static int set_instance_transforms(rayhip_ctx *c, const VertexStamps &st, const 
     if (!r.slot_flags.empty()) {
         HIP_TRY(hipMemsetAsync(r.d_slot_claim.p, 0, r.slot_flags.size() * sizeof(uint32_t), s));
     }
-    ri::k_pose_instances<<<(n + 255) / 256, 256, 0, s>>>(d_slots, d_xforms, n, (reinterpret_cast<uintptr_t>(d_xforms) & 15u) == 0u, r.d_slot_flags.as<uint8_t>(),
-                                                        r.d_slot_claim.as<uint32_t>(), d_instances, c->instances_count, !c->light_refit.on, d_staged,
-                                                        d_staged_slots, d_counters);
+    ri::k_pose_instances<<<blocks_of(n), 256, 0, s>>>(d_slots, d_xforms, n, (reinterpret_cast<uintptr_t>(d_xforms) & 15u) == 0u, r.d_slot_flags.as<uint8_t>(),
+                                                      r.d_slot_claim.as<uint32_t>(), d_instances, c->instances_count, !c->light_refit.on, d_staged,
+                                                      d_staged_slots, d_counters);
     HIP_TRY(hipGetLastError());
     uint32_t findings[ri::N_FINDINGS] = {};
     HIP_TRY(hipMemcpyAsync(findings, d_counters, sizeof(findings), hipMemcpyDeviceToHost, s));
@@ -568,11 +639,11 @@ static int set_instance_transforms(rayhip_ctx *c, const VertexStamps &st, const 
         return 2;
     }
     // (the counters are back and zero: from here on the live instance array is written)
-    ri::k_commit_instances<<<(n + 255) / 256, 256, 0, s>>>(d_staged, d_staged_slots, n, d_instances, c->instances_count);
+    ri::k_commit_instances<<<blocks_of(n), 256, 0, s>>>(d_staged, d_staged_slots, n, d_instances, c->instances_count);
     HIP_TRY(hipGetLastError());
     if (n_live) {
-        ri::k_instance_boxes<<<(n_live + 255) / 256, 256, 0, s>>>(r.d_live.as<uint32_t>(), n_live, d_instances, c->instances_count, c->nodes.as<rayhip_bvh2_node>(),
-                                                                c->nodes_used, d_boxes);
+        ri::k_instance_boxes<<<blocks_of(n_live), 256, 0, s>>>(r.d_live.as<uint32_t>(), n_live, d_instances, c->instances_count, c->nodes.as<rayhip_bvh2_node>(),
+                                                               c->nodes_used, d_boxes);
         HIP_TRY(hipGetLastError());
     }
     std::vector<uint8_t> back(stage_bytes);
@@ -600,28 +671,13 @@ static int set_instance_transforms(rayhip_ctx *c, const VertexStamps &st, const 
     if (n_live) {
         memcpy(up.boxes.data(), back.data() + boxes_at, size_t(n_live) * sizeof(rayhip_lbvh::Box));
     }
-    uint32_t tlas_root = 0xffffffffu;
-    rayhip_lbvh::Box root_box = rayhip_lbvh::empty_box();
-    if (const int rc = rebuild_top_level(c, up, tlas_root, root_box)) {
-        return rc == 2 ? fail("%s: %s", st.who, std::string(g_err).c_str()) : rc; // (the instance array is the new one already: an error)
-    }
-    refresh_top_level_view(c, tlas_root, root_box, n_live);
-    HIP_TRY(st.stamp("top level built"));
-    return 0;
+    return rebuild_top_level_behind(c, up, st);
 }
 
 // what both forms check before anything else: 0 = go on, 1 / 2 = the return code
 static int instance_move_possible(rayhip_ctx *c, const char *who, const uint32_t n, const void *slots, const void *xforms) {
-    if (n > 0 && (!slots || !xforms)) {
-        return fail("%s: a null pointer", who);
-    }
-    if (!c->have_scene) {
-        (void)fail("%s before rayhip_scene_upload", who);
-        return 2;
-    }
-    if (c->wide == 8) {
-        (void)fail("%s: the context walks the 8-wide tree, whose builder runs on the host only", who);
-        return 2;
+    if (const int rc = scene_change_possible(c, who, n > 0 && (!slots || !xforms), true)) {
+        return rc;
     }
     if (c->refit.slot_flags.size() != c->instances_count || c->refit.instances.size() != c->instances_count) { // (an upload that failed half-way)
         (void)fail("%s: the tables of the last upload are incomplete", who);
@@ -634,43 +690,11 @@ static int instance_move_possible(rayhip_ctx *c, const char *who, const uint32_t
 }
 
 int rayhip_scene_set_instance_transforms(rayhip_ctx *c, uint32_t n, const uint32_t *slots, const float *xforms) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (const int rc = instance_move_possible(c, "rayhip_scene_set_instance_transforms", n, slots, xforms)) {
-        return rc;
-    }
-    if (n == 0) {
-        return 0;
-    }
-    const VertexStamps st{c, "rayhip_scene_set_instance_transforms"};
-    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
-    HIP_TRY(st.stamp("begin"));
-    // the caller's arrays onto the device: [n] matrices, [n] slots
-    if (c->instance_args.alloc(size_t(n) * 68)) {
-        return 1;
-    }
-    float *d_xforms = c->instance_args.as<float>();
-    uint32_t *d_slots = reinterpret_cast<uint32_t *>(c->instance_args.as<uint8_t>() + size_t(n) * 64);
-    HIP_TRY(hipMemcpyAsync(d_xforms, xforms, size_t(n) * 64, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_slots, slots, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
-    return set_instance_transforms(c, st, n, d_slots, d_xforms); // (it waits for the stream before it returns: the arrays may go away)
+    return set_records(c, "rayhip_scene_set_instance_transforms", n, slots, xforms, &rayhip_ctx::instance_args, instance_move_possible, set_instance_transforms);
 }
 
 int rayhip_scene_set_instance_transforms_device(rayhip_ctx *c, uint32_t n, const uint32_t *device_slots, const float *device_xforms) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (const int rc = instance_move_possible(c, "rayhip_scene_set_instance_transforms_device", n, device_slots, device_xforms)) {
-        return rc;
-    }
-    if (n == 0) {
-        return 0;
-    }
-    const VertexStamps st{c, "rayhip_scene_set_instance_transforms_device"};
-    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
-    HIP_TRY(st.stamp("begin"));
-    return set_instance_transforms(c, st, n, device_slots, device_xforms);
+    return set_records(c, "rayhip_scene_set_instance_transforms_device", n, device_slots, device_xforms, nullptr, instance_move_possible, set_instance_transforms);
 }
 
 // ---- analytic lights that move or change colour: records in, leaf summaries on the device, the light tree refitted (light_pose.h) ----
@@ -698,9 +722,9 @@ static int set_lights(rayhip_ctx *c, const VertexStamps &st, const uint32_t n, c
     if (lr.lights_count) {
         HIP_TRY(hipMemsetAsync(lr.claim.p, 0, size_t(lr.lights_count) * sizeof(uint32_t), s));
     }
-    lp::k_pose_lights<<<(n + 255) / 256, 256, 0, s>>>(d_slots, d_records, n, (reinterpret_cast<uintptr_t>(d_records) & 15u) == 0u, c->lights.as<rayhip_light>(),
-                                                     lr.lights_count, lr.live.as<uint8_t>(), lr.claim.as<uint32_t>(), d_staged, d_staged_leaf, d_staged_slots,
-                                                     d_counters);
+    lp::k_pose_lights<<<blocks_of(n), 256, 0, s>>>(d_slots, d_records, n, (reinterpret_cast<uintptr_t>(d_records) & 15u) == 0u, c->lights.as<rayhip_light>(),
+                                                   lr.lights_count, lr.live.as<uint8_t>(), lr.claim.as<uint32_t>(), d_staged, d_staged_leaf, d_staged_slots,
+                                                   d_counters);
     HIP_TRY(hipGetLastError());
     uint32_t findings[lp::N_FINDINGS] = {};
     HIP_TRY(hipMemcpyAsync(findings, d_counters, sizeof(findings), hipMemcpyDeviceToHost, s));
@@ -722,8 +746,8 @@ static int set_lights(rayhip_ctx *c, const VertexStamps &st, const uint32_t n, c
         return fail("%s: %u records have a colour or a parameter that is not finite", st.who, findings[lp::NOT_FINITE]);
     }
     // (the counters are back and zero: from here on the live light arrays are written)
-    lp::k_commit_lights<<<(n + 255) / 256, 256, 0, s>>>(d_staged, d_staged_leaf, d_staged_slots, n, c->lights.as<rayhip_light>(),
-                                                       lr.leaf.as<rayhip_light_refit::Summary>(), lr.posed.as<uint8_t>(), lr.lights_count);
+    lp::k_commit_lights<<<blocks_of(n), 256, 0, s>>>(d_staged, d_staged_leaf, d_staged_slots, n, c->lights.as<rayhip_light>(),
+                                                     lr.leaf.as<rayhip_light_refit::Summary>(), lr.posed.as<uint8_t>(), lr.lights_count);
     HIP_TRY(hipGetLastError());
     HIP_TRY(st.stamp("lights committed"));
     // the level launches read the summary of EVERY leaf.  Those of the triangle lights are written by the first pass over them, not when
@@ -744,12 +768,8 @@ static int set_lights(rayhip_ctx *c, const VertexStamps &st, const uint32_t n, c
 
 // what both forms check before anything else: 0 = go on, 1 / 2 = the return code
 static int light_move_possible(rayhip_ctx *c, const char *who, const uint32_t n, const void *slots, const void *records) {
-    if (n > 0 && (!slots || !records)) {
-        return fail("%s: a null pointer", who);
-    }
-    if (!c->have_scene) {
-        (void)fail("%s before rayhip_scene_upload", who);
-        return 2;
+    if (const int rc = scene_change_possible(c, who, n > 0 && (!slots || !records), false)) { // (no tree of the geometry is rebuilt)
+        return rc;
     }
     if (!c->light_refit.on || !c->light_refit.ready) {
         (void)fail("%s: rayhip_scene_refit_lights is off, or its tables are not prepared; the switch keeps the light tree refittable", who);
@@ -759,43 +779,35 @@ static int light_move_possible(rayhip_ctx *c, const char *who, const uint32_t n,
 }
 
 int rayhip_scene_set_lights(rayhip_ctx *c, uint32_t n, const uint32_t *slots, const rayhip_light *records) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (const int rc = light_move_possible(c, "rayhip_scene_set_lights", n, slots, records)) {
-        return rc;
-    }
-    if (n == 0) {
-        return 0;
-    }
-    const VertexStamps st{c, "rayhip_scene_set_lights"};
-    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
-    HIP_TRY(st.stamp("begin"));
-    // the caller's arrays onto the device: [n] records, [n] slots
-    if (c->light_args.alloc(size_t(n) * 68)) {
-        return 1;
-    }
-    rayhip_light *d_records = c->light_args.as<rayhip_light>();
-    uint32_t *d_slots = reinterpret_cast<uint32_t *>(c->light_args.as<uint8_t>() + size_t(n) * 64);
-    HIP_TRY(hipMemcpyAsync(d_records, records, size_t(n) * 64, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_slots, slots, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
-    return set_lights(c, st, n, d_slots, d_records); // (it waits for the stream before it returns: the arrays may go away)
+    return set_records(c, "rayhip_scene_set_lights", n, slots, records, &rayhip_ctx::light_args, light_move_possible, set_lights);
 }
 
 int rayhip_scene_set_lights_device(rayhip_ctx *c, uint32_t n, const uint32_t *device_slots, const rayhip_light *device_records) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (const int rc = light_move_possible(c, "rayhip_scene_set_lights_device", n, device_slots, device_records)) {
+    return set_records(c, "rayhip_scene_set_lights_device", n, device_slots, device_records, nullptr, light_move_possible, set_lights);
+}
+
+// ---- handles over vertex ranges: what creating and destroying a skin, a morph set and a normal set share ----------------------------
+// (the records and their tables: rayhip_ctx::RangeHead, RangeTable.)  A create asks, in this order: its pointers; the context and the
+// range (range_possible); what only its kind knows of the description's sizes; a free slot clear of the live records
+// (RangeTable::free_slot); the description's arrays; the pinned light vertices (range_not_pinned) -- and issues the handle
+// (RangeTable::issue) when its tables are on the device.  A destroy is RangeTable::destroy.
+static int range_possible(rayhip_ctx *c, const char *who, const uint32_t first, const uint32_t count) {
+    if (const int rc = vertex_update_possible(c, who)) {
         return rc;
     }
-    if (n == 0) {
-        return 0;
+    if (count == 0 || uint64_t(first) + count > c->geometry.vertices) {
+        return outside_the_scene(c, who, first, count);
     }
-    const VertexStamps st{c, "rayhip_scene_set_lights_device"};
-    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
-    HIP_TRY(st.stamp("begin"));
-    return set_lights(c, st, n, device_slots, device_records);
+    return 0;
+}
+
+// `mover`: what would move the vertices of the range -- it may put them anywhere
+static int range_not_pinned(rayhip_ctx *c, const char *who, const uint32_t first, const uint32_t count, const char *mover) {
+    if (const uint32_t *pinned = pinned_light_vertex(c, first, count, nullptr)) {
+        (void)fail("%s: vertex %u belongs to a triangle light; lights are not rebuilt by %s", who, *pinned, mover);
+        return 2;
+    }
+    return 0;
 }
 
 // ---- the skins ---------------------------------------------------------------------------------------------------------------------------
@@ -806,26 +818,15 @@ int rayhip_skin_create(rayhip_ctx *c, const rayhip_skin_desc *d, int *out_skin) 
     if (!d || !out_skin || !d->bone_indices || !d->bone_weights) {
         return fail("rayhip_skin_create: a null pointer");
     }
-    if (const int rc = vertex_update_possible(c, "rayhip_skin_create")) {
+    if (const int rc = range_possible(c, "rayhip_skin_create", d->first_vertex, d->count)) {
         return rc;
-    }
-    if (d->count == 0 || uint64_t(d->first_vertex) + d->count > c->geometry.vertices) {
-        return outside_the_scene(c, "rayhip_skin_create", d->first_vertex, d->count);
     }
     if (d->bones_count == 0 || d->bones_count > 65536u) {
         return fail("rayhip_skin_create: %u bones (bone indices are 16-bit)", d->bones_count);
     }
     int slot = -1;
-    for (int k = int(rayhip_skin::MAX_SKINS) - 1; k >= 0; --k) {
-        const rayhip_ctx::Skin &o = c->skins[k];
-        if (!o.live) {
-            slot = k;
-        } else if (d->first_vertex < o.first + o.count && o.first < d->first_vertex + d->count) {
-            return fail("rayhip_skin_create: vertices [%u, %u + %u) overlap skin %d", d->first_vertex, d->first_vertex, d->count, o.id);
-        }
-    }
-    if (slot < 0) {
-        return fail("rayhip_skin_create: %u skins are live already", rayhip_skin::MAX_SKINS);
+    if (c->skins.free_slot("rayhip_skin_create", d->first_vertex, d->count, slot)) {
+        return 1;
     }
     {
         uint32_t where = 0;
@@ -834,11 +835,10 @@ int rayhip_skin_create(rayhip_ctx *c, const rayhip_skin_desc *d, int *out_skin) 
                             : fail("rayhip_skin_create: a weight of vertex %u is negative or not finite", d->first_vertex + where);
         }
     }
-    if (const uint32_t *pinned = pinned_light_vertex(c, d->first_vertex, d->count, nullptr)) { // (a pose may put it anywhere)
-        (void)fail("rayhip_skin_create: vertex %u belongs to a triangle light; lights are not rebuilt by a pose", *pinned);
-        return 2;
+    if (const int rc = range_not_pinned(c, "rayhip_skin_create", d->first_vertex, d->count, "a pose")) {
+        return rc;
     }
-    rayhip_ctx::Skin &k = c->skins[slot];
+    rayhip_ctx::Skin &k = c->skins.slots[slot];
     const size_t n = d->count;
     if (k.rest.alloc(n * sizeof(rayhip_vertex)) || upload(c, k.indices, d->bone_indices, n * 4 * sizeof(uint16_t)) ||
         upload(c, k.weights, d->bone_weights, n * 4 * sizeof(float))) {
@@ -847,135 +847,12 @@ int rayhip_skin_create(rayhip_ctx *c, const rayhip_skin_desc *d, int *out_skin) 
     HIP_TRY(hipMemcpyAsync(k.rest.p, d->rest ? static_cast<const void *>(d->rest) : static_cast<const void *>(c->vertices.as<rayhip_vertex>() + d->first_vertex),
                            n * sizeof(rayhip_vertex), d->rest ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream)); // the caller's arrays may go away after this call
-    c->skin_serial = (c->skin_serial % 0x7ffffffu) + 1; // (1 .. 2^27 - 1: the handle stays a positive int, and is never a return code)
-    k.live = true, k.id = int(c->skin_serial << 4) | slot, k.first = d->first_vertex, k.count = d->count, k.bones_count = d->bones_count;
-    *out_skin = k.id;
+    k.bones_count = d->bones_count;
+    *out_skin = c->skins.issue(slot, d->first_vertex, d->count);
     return 0;
 }
 
-int rayhip_skin_destroy(rayhip_ctx *c, int skin) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (!c->skin_of(skin)) {
-        (void)fail("rayhip_skin_destroy: skin %d is not live", skin);
-        return 2;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    rayhip_ctx::Skin &k = *c->skin_of(skin);
-    k.live = false;
-    k.rest.release(), k.indices.release(), k.weights.release();
-    return 0;
-}
-
-// ---- what the two pose calls share (rayhip_scene_pose_skins, rayhip_scene_pose): the staging array, the counter, the copies, the refit ----
-// vertices [first, first + count) of the scene, posed into the staging array from record `at` on
-struct StagedRange {
-    uint32_t first, count;
-    size_t at;
-};
-
-// waits for pending passes, stamps "begin", and makes room: `stage_vertices` staged records, `floats` of palettes and weights, the counters (zeroed)
-static int pose_begin(rayhip_ctx *c, const VertexStamps &st, const size_t stage_vertices, const size_t floats) {
-    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
-    HIP_TRY(st.stamp("begin"));
-    if (c->skin_stage.alloc(stage_vertices * sizeof(rayhip_vertex)) || c->skin_palettes.alloc(floats * sizeof(float)) || c->skin_counters.alloc(2 * sizeof(uint32_t))) {
-        return 1;
-    }
-    HIP_TRY(hipMemsetAsync(c->skin_counters.as<uint32_t>(), 0, 2 * sizeof(uint32_t), c->stream));
-    return 0;
-}
-
-// k_skin_vertices over vertices [off, off + count) of skin `k` (its pointers offset: 8-byte index records and 16-byte weight records stay
-// aligned at any vertex), posed into the staging array where the skin's range begins at record `at`
-static int launch_skin_segment(rayhip_ctx *c, const rayhip_ctx::Skin &k, const uint32_t off, const uint32_t count, const float *d_palette, const size_t at) {
-    if (count == 0) {
-        return 0;
-    }
-    rayhip_skin::k_skin_vertices<<<(count + 255) / 256, 256, 0, c->stream>>>(k.rest.as<rayhip_vertex>() + off, k.indices.as<uint16_t>() + size_t(off) * 4,
-                                                                            k.weights.as<float>() + size_t(off) * 4, count, d_palette, k.bones_count,
-                                                                            c->refit.d_vertex_used.as<uint8_t>() + k.first + off,
-                                                                            c->skin_stage.as<rayhip_vertex>() + at + off, c->skin_counters.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// behind the launches: the counter comes back; where it is zero the staged ranges are copied into the vertex array and ONE refit follows
-static int pose_commit(rayhip_ctx *c, const VertexStamps &st, const std::vector<StagedRange> &staged) {
-    hipStream_t s = c->stream;
-    uint32_t counters[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(counters, c->skin_counters.as<uint32_t>(), sizeof(counters), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s)); // (the caller's palettes and weights may go away after this)
-    HIP_TRY(st.stamp("vertices posed"));
-    if (counters[0] != 0) {
-        return fail("%s: the posed position of %u vertices is not finite", st.who, counters[0]);
-    }
-    // (the counter is back and zero: from here on the live vertex array is written)
-    for (const StagedRange &r : staged) {
-        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + r.first, c->skin_stage.as<rayhip_vertex>() + r.at, size_t(r.count) * sizeof(rayhip_vertex),
-                               hipMemcpyDeviceToDevice, s));
-    }
-    HIP_TRY(st.stamp("vertices copied"));
-    return refit_after_vertices(c, st);
-}
-
-int rayhip_scene_pose_skins(rayhip_ctx *c, int n, const int *skins, const float *const *palettes) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (n < 0 || n > int(rayhip_skin::MAX_SKINS) || (n > 0 && (!skins || !palettes))) {
-        return fail("rayhip_scene_pose_skins: bad arguments");
-    }
-    if (const int rc = vertex_update_possible(c, "rayhip_scene_pose_skins")) {
-        return rc;
-    }
-    size_t stage_vertices = 0, palette_floats = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!c->skin_of(skins[i])) {
-            (void)fail("rayhip_scene_pose_skins: skin %d is not live", skins[i]);
-            return 2;
-        }
-        if (!palettes[i]) {
-            return fail("rayhip_scene_pose_skins: no palette for skin %d", skins[i]);
-        }
-        for (int j = 0; j < i; ++j) {
-            if (skins[j] == skins[i]) {
-                return fail("rayhip_scene_pose_skins: skin %d is named twice", skins[i]);
-            }
-        }
-        stage_vertices += c->skin_of(skins[i])->count, palette_floats += size_t(c->skin_of(skins[i])->bones_count) * 12;
-    }
-    for (int i = 0; i < n; ++i) { // (cannot occur without a live morph set)
-        const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
-        for (const rayhip_ctx::Morph &m : c->morphs) {
-            if (m.live && m.first < k.first + k.count && k.first < m.first + m.count) {
-                return fail("rayhip_scene_pose_skins: skin %d holds morph set %d; pose them together (rayhip_scene_pose)", k.id, m.id);
-            }
-        }
-    }
-    if (n == 0) {
-        return 0;
-    }
-    const VertexStamps st{c, "rayhip_scene_pose_skins"};
-    if (pose_begin(c, st, stage_vertices, palette_floats)) {
-        return 1;
-    }
-    std::vector<StagedRange> staged;
-    {
-        size_t at_vertex = 0, at_float = 0;
-        for (int i = 0; i < n; ++i) {
-            const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
-            float *d_palette = c->skin_palettes.as<float>() + at_float;
-            HIP_TRY(hipMemcpyAsync(d_palette, palettes[i], size_t(k.bones_count) * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-            if (launch_skin_segment(c, k, 0, k.count, d_palette, at_vertex)) {
-                return 1;
-            }
-            staged.push_back({k.first, k.count, at_vertex});
-            at_vertex += k.count, at_float += size_t(k.bones_count) * 12;
-        }
-    }
-    return pose_commit(c, st, staged);
-}
+int rayhip_skin_destroy(rayhip_ctx *c, int skin) { return !c || use_device(c) ? 1 : c->skins.destroy(c->stream, "rayhip_skin_destroy", skin); }
 
 // ---- morph sets (morph.h, morph.hip.h) ------------------------------------------------------------------------------------------------------
 int rayhip_morph_create(rayhip_ctx *c, const rayhip_morph_desc *d, int *out_morph) {
@@ -985,26 +862,15 @@ int rayhip_morph_create(rayhip_ctx *c, const rayhip_morph_desc *d, int *out_morp
     if (!d || !out_morph || !d->targets) {
         return fail("rayhip_morph_create: a null pointer");
     }
-    if (const int rc = vertex_update_possible(c, "rayhip_morph_create")) {
+    if (const int rc = range_possible(c, "rayhip_morph_create", d->first_vertex, d->count)) {
         return rc;
-    }
-    if (d->count == 0 || uint64_t(d->first_vertex) + d->count > c->geometry.vertices) {
-        return outside_the_scene(c, "rayhip_morph_create", d->first_vertex, d->count);
     }
     if (d->targets_count == 0 || d->targets_count > rayhip_morph::MAX_TARGETS) {
         return fail("rayhip_morph_create: %u targets (1 .. %u)", d->targets_count, rayhip_morph::MAX_TARGETS);
     }
     int slot = -1;
-    for (int k = int(rayhip_morph::MAX_MORPHS) - 1; k >= 0; --k) {
-        const rayhip_ctx::Morph &o = c->morphs[k];
-        if (!o.live) {
-            slot = k;
-        } else if (d->first_vertex < o.first + o.count && o.first < d->first_vertex + d->count) {
-            return fail("rayhip_morph_create: vertices [%u, %u + %u) overlap morph set %d", d->first_vertex, d->first_vertex, d->count, o.id);
-        }
-    }
-    if (slot < 0) {
-        return fail("rayhip_morph_create: %u morph sets are live already", rayhip_morph::MAX_MORPHS);
+    if (c->morphs.free_slot("rayhip_morph_create", d->first_vertex, d->count, slot)) {
+        return 1;
     }
     {
         uint32_t where = 0;
@@ -1015,14 +881,13 @@ int rayhip_morph_create(rayhip_ctx *c, const rayhip_morph_desc *d, int *out_morp
                               : fail("rayhip_morph_create: more than 2^32 - 1 entries in all");
         }
     }
-    if (const uint32_t *pinned = pinned_light_vertex(c, d->first_vertex, d->count, nullptr)) { // (a pose may put it anywhere)
-        (void)fail("rayhip_morph_create: vertex %u belongs to a triangle light; lights are not rebuilt by a pose", *pinned);
-        return 2;
+    if (const int rc = range_not_pinned(c, "rayhip_morph_create", d->first_vertex, d->count, "a pose")) {
+        return rc;
     }
     std::vector<uint32_t> row;
     std::vector<rayhip_morph::Entry> entries;
     rayhip_morph::build_rows(d->targets, d->targets_count, d->count, row, entries);
-    rayhip_ctx::Morph &m = c->morphs[slot];
+    rayhip_ctx::Morph &m = c->morphs.slots[slot];
     const size_t n = d->count;
     if (m.base.alloc(n * sizeof(rayhip_vertex)) || upload(c, m.row, row.data(), row.size() * sizeof(uint32_t)) ||
         upload(c, m.entries, entries.data(), entries.size() * sizeof(rayhip_morph::Entry))) {
@@ -1031,26 +896,12 @@ int rayhip_morph_create(rayhip_ctx *c, const rayhip_morph_desc *d, int *out_morp
     HIP_TRY(hipMemcpyAsync(m.base.p, d->base ? static_cast<const void *>(d->base) : static_cast<const void *>(c->vertices.as<rayhip_vertex>() + d->first_vertex),
                            n * sizeof(rayhip_vertex), d->base ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream)); // the table and the caller's arrays may go away after this call
-    c->morph_serial = (c->morph_serial % 0x7ffffffu) + 1; // (as a skin's handle)
-    m.live = true, m.id = int(c->morph_serial << 4) | slot, m.first = d->first_vertex, m.count = d->count, m.targets_count = d->targets_count;
-    *out_morph = m.id;
+    m.targets_count = d->targets_count;
+    *out_morph = c->morphs.issue(slot, d->first_vertex, d->count);
     return 0;
 }
 
-int rayhip_morph_destroy(rayhip_ctx *c, int morph) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (!c->morph_of(morph)) {
-        (void)fail("rayhip_morph_destroy: morph set %d is not live", morph);
-        return 2;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    rayhip_ctx::Morph &m = *c->morph_of(morph);
-    m.live = false;
-    m.base.release(), m.row.release(), m.entries.release();
-    return 0;
-}
+int rayhip_morph_destroy(rayhip_ctx *c, int morph) { return !c || use_device(c) ? 1 : c->morphs.destroy(c->stream, "rayhip_morph_destroy", morph); }
 
 // ---- normal sets (normals.h, normals.hip.h) ---------------------------------------------------------------------------------------------------
 // The topology is read back once, here: the nodes, the entry table and the indices as they are on the device (the leaf refinement of an
@@ -1062,23 +913,12 @@ int rayhip_normals_create(rayhip_ctx *c, const rayhip_normals_desc *d, int *out_
     if (!d || !out_set) {
         return fail("rayhip_normals_create: a null pointer");
     }
-    if (const int rc = vertex_update_possible(c, "rayhip_normals_create")) {
+    if (const int rc = range_possible(c, "rayhip_normals_create", d->first_vertex, d->count)) {
         return rc;
     }
-    if (d->count == 0 || uint64_t(d->first_vertex) + d->count > c->geometry.vertices) {
-        return outside_the_scene(c, "rayhip_normals_create", d->first_vertex, d->count);
-    }
     int slot = -1;
-    for (int k = int(rayhip_normals::MAX_SETS) - 1; k >= 0; --k) {
-        const rayhip_ctx::Normals &o = c->normal_sets[k];
-        if (!o.live) {
-            slot = k;
-        } else if (d->first_vertex < o.first + o.count && o.first < d->first_vertex + d->count) {
-            return fail("rayhip_normals_create: vertices [%u, %u + %u) overlap normal set %d", d->first_vertex, d->first_vertex, d->count, o.id);
-        }
-    }
-    if (slot < 0) {
-        return fail("rayhip_normals_create: %u normal sets are live already", rayhip_normals::MAX_SETS);
+    if (c->normal_sets.free_slot("rayhip_normals_create", d->first_vertex, d->count, slot)) {
+        return 1;
     }
     {
         uint32_t where = 0;
@@ -1088,16 +928,15 @@ int rayhip_normals_create(rayhip_ctx *c, const rayhip_normals_desc *d, int *out_
                               : fail("rayhip_normals_create: the weld index of vertex %u is not canonical (weld[weld[i]] != weld[i])", d->first_vertex + where);
         }
     }
-    if (const uint32_t *pinned = pinned_light_vertex(c, d->first_vertex, d->count, nullptr)) { // (the skins' rule)
-        (void)fail("rayhip_normals_create: vertex %u belongs to a triangle light; lights are not rebuilt by a recompute", *pinned);
-        return 2;
+    if (const int rc = range_not_pinned(c, "rayhip_normals_create", d->first_vertex, d->count, "a recompute")) {
+        return rc;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     std::vector<rayhip_bvh2_node> nodes(c->nodes_used);
     std::vector<uint32_t> tri_indices(c->refit.entries), vtx_indices(c->geometry.vtx_indices);
-    auto back = [&](void *dst, const DevBuf &src, const size_t bytes) { return bytes == 0 || hipMemcpy(dst, src.p, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
-    if (!back(nodes.data(), c->nodes, nodes.size() * sizeof(rayhip_bvh2_node)) || !back(tri_indices.data(), c->tri_indices, tri_indices.size() * sizeof(uint32_t)) ||
-        !back(vtx_indices.data(), c->vtx_indices, vtx_indices.size() * sizeof(uint32_t))) {
+    if (!read_back(nodes.data(), c->nodes, nodes.size() * sizeof(rayhip_bvh2_node)) ||
+        !read_back(tri_indices.data(), c->tri_indices, tri_indices.size() * sizeof(uint32_t)) ||
+        !read_back(vtx_indices.data(), c->vtx_indices, vtx_indices.size() * sizeof(uint32_t))) {
         return fail("rayhip_normals_create: reading the topology back failed");
     }
     std::vector<uint32_t> reachable;
@@ -1110,152 +949,157 @@ int rayhip_normals_create(rayhip_ctx *c, const rayhip_normals_desc *d, int *out_
                                    (d->flags & RAYHIP_NORMALS_N) ? d->weld : nullptr, tb)) {
         return fail("rayhip_normals_create: more than 2^32 - 1 row entries");
     }
-    rayhip_ctx::Normals &n = c->normal_sets[slot];
+    rayhip_ctx::Normals &n = c->normal_sets.slots[slot];
     const bool welded = !tb.wrow.empty();
     if (upload(c, n.faces, tb.faces.data(), tb.faces.size() * sizeof(uint32_t)) || upload(c, n.row, tb.row.data(), tb.row.size() * sizeof(uint32_t)) ||
         upload(c, n.entries, tb.entries.data(), tb.entries.size() * sizeof(uint32_t)) ||
         (welded && (upload(c, n.wrow, tb.wrow.data(), tb.wrow.size() * sizeof(uint32_t)) ||
                     upload(c, n.wentries, tb.wentries.data(), tb.wentries.size() * sizeof(uint32_t)))) ||
         n.frames.alloc(tb.faces.size() * sizeof(rayhip_normals::FaceFrame))) {
-        rayhip_ctx::release_normals(n);
+        n.release();
         return 1;
     }
     HIP_TRY(hipStreamSynchronize(c->stream)); // the tables go out of scope
-    c->normals_serial = (c->normals_serial % 0x7ffffffu) + 1; // (as a skin's handle)
-    n.live = true, n.id = int(c->normals_serial << 4) | slot, n.first = d->first_vertex, n.count = d->count, n.flags = d->flags;
-    n.faces_count = uint32_t(tb.faces.size()), n.welded = welded;
-    *out_set = n.id;
+    n.flags = d->flags, n.faces_count = uint32_t(tb.faces.size()), n.welded = welded;
+    *out_set = c->normal_sets.issue(slot, d->first_vertex, d->count);
     return 0;
 }
 
-int rayhip_normals_destroy(rayhip_ctx *c, int set) {
-    if (!c || use_device(c)) {
-        return 1;
+int rayhip_normals_destroy(rayhip_ctx *c, int set) { return !c || use_device(c) ? 1 : c->normal_sets.destroy(c->stream, "rayhip_normals_destroy", set); }
+
+// ---- the poses (rayhip_scene_pose_skins, rayhip_scene_pose): morph sets and skins posed into a staging array, then ONE refit -------------
+// vertices [first, first + count) of the scene, posed into the staging array from record `at` on
+struct StagedRange {
+    uint32_t first, count;
+    size_t at;
+};
+
+// k_skin_vertices over vertices [off, off + count) of skin `k` (its pointers offset: 8-byte index records and 16-byte weight records stay
+// aligned at any vertex), posed into the staging array where the skin's range begins at record `at`
+static int launch_skin_segment(rayhip_ctx *c, const rayhip_ctx::Skin &k, const uint32_t off, const uint32_t count, const float *d_palette, const size_t at) {
+    if (count == 0) {
+        return 0;
     }
-    if (!c->normals_of(set)) {
-        (void)fail("rayhip_normals_destroy: normal set %d is not live", set);
-        return 2;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    rayhip_ctx::release_normals(*c->normals_of(set));
+    rayhip_skin::k_skin_vertices<<<blocks_of(count), 256, 0, c->stream>>>(k.rest.as<rayhip_vertex>() + off, k.indices.as<uint16_t>() + size_t(off) * 4,
+                                                                          k.weights.as<float>() + size_t(off) * 4, count, d_palette, k.bones_count,
+                                                                          c->refit.d_vertex_used.as<uint8_t>() + k.first + off,
+                                                                          c->skin_stage.as<rayhip_vertex>() + at + off, c->skin_counters.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
 // Morph sets and skins in one pose.  A skin's range is staged as a sequence of launches over segments -- [plain][set A][plain][set B]... --
 // plain ones by k_skin_vertices with its pointers offset, covered ones by the fused kernel: no kernel looks for the set it is in.
-int rayhip_scene_pose(rayhip_ctx *c, int n_morphs, const int *morphs, const float *const *weights, int n_skins, const int *skins, const float *const *palettes) {
-    if (!c || use_device(c)) {
-        return 1;
-    }
-    if (n_morphs < 0 || n_morphs > int(rayhip_morph::MAX_MORPHS) || n_skins < 0 || n_skins > int(rayhip_skin::MAX_SKINS) ||
-        (n_morphs > 0 && (!morphs || !weights)) || (n_skins > 0 && (!skins || !palettes))) {
-        return fail("rayhip_scene_pose: bad arguments");
-    }
-    if (n_morphs == 0 && n_skins == 0) {
-        return 0;
-    }
-    if (const int rc = vertex_update_possible(c, "rayhip_scene_pose")) {
-        return rc;
-    }
+// The entry points have checked the counts and the outer pointers and asked vertex_update_possible, each in its own order.
+// `who`: the entry point the texts and stamps name; `together`: how its text tells the caller to pose a skin with the sets it holds.
+static int pose_ranges(rayhip_ctx *c, const char *who, const char *together, const int n_morphs, const int *morphs, const float *const *weights, const int n_skins,
+                       const int *skins, const float *const *palettes) {
     size_t stage_vertices = 0, floats = 0;
     for (int i = 0; i < n_morphs; ++i) {
-        const rayhip_ctx::Morph *m = c->morph_of(morphs[i]);
+        const rayhip_ctx::Morph *m = c->morphs.of(morphs[i]);
         if (!m) {
-            (void)fail("rayhip_scene_pose: morph set %d is not live", morphs[i]);
+            (void)fail("%s: morph set %d is not live", who, morphs[i]);
             return 2;
         }
         if (!weights[i]) {
-            return fail("rayhip_scene_pose: no weights for morph set %d", morphs[i]);
+            return fail("%s: no weights for morph set %d", who, morphs[i]);
         }
         for (int j = 0; j < i; ++j) {
             if (morphs[j] == morphs[i]) {
-                return fail("rayhip_scene_pose: morph set %d is named twice", morphs[i]);
+                return fail("%s: morph set %d is named twice", who, morphs[i]);
             }
         }
         for (uint32_t t = 0; t < m->targets_count; ++t) {
             if (!rayhip_skin::finite_f(weights[i][t])) {
-                return fail("rayhip_scene_pose: the weight of target %u of morph set %d is not finite", t, morphs[i]);
+                return fail("%s: the weight of target %u of morph set %d is not finite", who, t, morphs[i]);
             }
         }
         floats += m->targets_count;
     }
     for (int i = 0; i < n_skins; ++i) {
-        if (!c->skin_of(skins[i])) {
-            (void)fail("rayhip_scene_pose: skin %d is not live", skins[i]);
+        if (!c->skins.of(skins[i])) {
+            (void)fail("%s: skin %d is not live", who, skins[i]);
             return 2;
         }
         if (!palettes[i]) {
-            return fail("rayhip_scene_pose: no palette for skin %d", skins[i]);
+            return fail("%s: no palette for skin %d", who, skins[i]);
         }
         for (int j = 0; j < i; ++j) {
             if (skins[j] == skins[i]) {
-                return fail("rayhip_scene_pose: skin %d is named twice", skins[i]);
+                return fail("%s: skin %d is named twice", who, skins[i]);
             }
         }
-        stage_vertices += c->skin_of(skins[i])->count, floats += size_t(c->skin_of(skins[i])->bones_count) * 12;
+        stage_vertices += c->skins.of(skins[i])->count, floats += size_t(c->skins.of(skins[i])->bones_count) * 12;
     }
     const auto named = [](const int *ids, const int n, const int id) { return std::find(ids, ids + n, id) != ids + n; };
     const auto overlap = [](const rayhip_ctx::Morph &m, const rayhip_ctx::Skin &k) { return m.first < k.first + k.count && k.first < m.first + m.count; };
     std::vector<bool> in_a_skin(size_t(n_morphs), false);
     for (int i = 0; i < n_morphs; ++i) {
-        const rayhip_ctx::Morph &m = *c->morph_of(morphs[i]);
+        const rayhip_ctx::Morph &m = *c->morphs.of(morphs[i]);
         for (const rayhip_ctx::Skin &k : c->skins) {
             if (!k.live || !overlap(m, k)) {
                 continue;
             }
             if (m.first < k.first || m.first + m.count > k.first + k.count) {
-                return fail("rayhip_scene_pose: morph set %d straddles the boundary of skin %d", m.id, k.id);
+                return fail("%s: morph set %d straddles the boundary of skin %d", who, m.id, k.id);
             }
             if (!named(skins, n_skins, k.id)) {
-                return fail("rayhip_scene_pose: morph set %d lies inside skin %d; pose them together", m.id, k.id);
+                return fail("%s: morph set %d lies inside skin %d; pose them together", who, m.id, k.id);
             }
             in_a_skin[size_t(i)] = true;
         }
         stage_vertices += in_a_skin[size_t(i)] ? 0 : m.count;
     }
     for (int i = 0; i < n_skins; ++i) {
-        const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
+        const rayhip_ctx::Skin &k = *c->skins.of(skins[i]);
         for (const rayhip_ctx::Morph &m : c->morphs) {
             if (m.live && overlap(m, k) && !named(morphs, n_morphs, m.id)) {
-                return fail("rayhip_scene_pose: skin %d holds morph set %d; pose them together", k.id, m.id);
+                return fail("%s: skin %d holds morph set %d; %s", who, k.id, m.id, together);
             }
         }
     }
-    const VertexStamps st{c, "rayhip_scene_pose"};
-    if (pose_begin(c, st, stage_vertices, floats)) {
+    if (n_morphs == 0 && n_skins == 0) {
+        return 0;
+    }
+    const VertexStamps st{c, who};
+    HIP_TRY(hipStreamSynchronize(c->stream)); // pending passes read the old arrays
+    HIP_TRY(st.stamp("begin"));
+    // room: the staged records, the palettes and weights, the counters (zeroed)
+    if (c->skin_stage.alloc(stage_vertices * sizeof(rayhip_vertex)) || c->skin_palettes.alloc(floats * sizeof(float)) || c->skin_counters.alloc(2 * sizeof(uint32_t))) {
         return 1;
     }
     hipStream_t s = c->stream;
     uint32_t *d_counters = c->skin_counters.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), s));
     const uint8_t *d_used = c->refit.d_vertex_used.as<uint8_t>();
     std::vector<StagedRange> staged;
     size_t at_vertex = 0, at_float = 0;
     std::vector<const float *> d_weights(size_t(n_morphs), nullptr);
     for (int i = 0; i < n_morphs; ++i) {
-        const rayhip_ctx::Morph &m = *c->morph_of(morphs[i]);
+        const rayhip_ctx::Morph &m = *c->morphs.of(morphs[i]);
         float *d_w = c->skin_palettes.as<float>() + at_float;
         HIP_TRY(hipMemcpyAsync(d_w, weights[i], size_t(m.targets_count) * sizeof(float), hipMemcpyHostToDevice, s));
         d_weights[size_t(i)] = d_w, at_float += m.targets_count;
     }
     for (int i = 0; i < n_skins; ++i) {
-        const rayhip_ctx::Skin &k = *c->skin_of(skins[i]);
+        const rayhip_ctx::Skin &k = *c->skins.of(skins[i]);
         float *d_palette = c->skin_palettes.as<float>() + at_float;
         HIP_TRY(hipMemcpyAsync(d_palette, palettes[i], size_t(k.bones_count) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
         std::vector<int> inside; // the named sets this skin holds, by first vertex
         for (int j = 0; j < n_morphs; ++j) {
-            if (overlap(*c->morph_of(morphs[j]), k)) {
+            if (overlap(*c->morphs.of(morphs[j]), k)) {
                 inside.push_back(j);
             }
         }
-        std::sort(inside.begin(), inside.end(), [&](const int x, const int y) { return c->morph_of(morphs[x])->first < c->morph_of(morphs[y])->first; });
+        std::sort(inside.begin(), inside.end(), [&](const int x, const int y) { return c->morphs.of(morphs[x])->first < c->morphs.of(morphs[y])->first; });
         uint32_t at = 0; // vertices of the skin staged so far
         for (const int j : inside) {
-            const rayhip_ctx::Morph &m = *c->morph_of(morphs[j]);
+            const rayhip_ctx::Morph &m = *c->morphs.of(morphs[j]);
             const uint32_t off = m.first - k.first;
             if (launch_skin_segment(c, k, at, off - at, d_palette, at_vertex)) {
                 return 1;
             }
-            rayhip_morph::k_morph_skin_vertices<<<(m.count + 255) / 256, 256, 0, s>>>(
+            rayhip_morph::k_morph_skin_vertices<<<blocks_of(m.count), 256, 0, s>>>(
                 m.base.as<rayhip_vertex>(), m.row.as<uint32_t>(), m.entries.as<rayhip_morph::Entry>(), m.count, d_weights[size_t(j)], m.targets_count,
                 k.indices.as<uint16_t>() + size_t(off) * 4, k.weights.as<float>() + size_t(off) * 4, d_palette, k.bones_count, d_used + m.first,
                 c->skin_stage.as<rayhip_vertex>() + at_vertex + off, d_counters);
@@ -1272,15 +1116,60 @@ int rayhip_scene_pose(rayhip_ctx *c, int n_morphs, const int *morphs, const floa
         if (in_a_skin[size_t(i)]) {
             continue;
         }
-        const rayhip_ctx::Morph &m = *c->morph_of(morphs[i]);
-        rayhip_morph::k_morph_vertices<<<(m.count + 255) / 256, 256, 0, s>>>(m.base.as<rayhip_vertex>(), m.row.as<uint32_t>(), m.entries.as<rayhip_morph::Entry>(),
-                                                                             m.count, d_weights[size_t(i)], m.targets_count, d_used + m.first,
-                                                                             c->skin_stage.as<rayhip_vertex>() + at_vertex, d_counters);
+        const rayhip_ctx::Morph &m = *c->morphs.of(morphs[i]);
+        rayhip_morph::k_morph_vertices<<<blocks_of(m.count), 256, 0, s>>>(m.base.as<rayhip_vertex>(), m.row.as<uint32_t>(), m.entries.as<rayhip_morph::Entry>(),
+                                                                          m.count, d_weights[size_t(i)], m.targets_count, d_used + m.first,
+                                                                          c->skin_stage.as<rayhip_vertex>() + at_vertex, d_counters);
         HIP_TRY(hipGetLastError());
         staged.push_back({m.first, m.count, at_vertex});
         at_vertex += m.count;
     }
-    return pose_commit(c, st, staged);
+    // behind the launches: the counter comes back; where it is zero the staged ranges are copied into the vertex array and ONE refit follows
+    uint32_t counters[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (the caller's palettes and weights may go away after this)
+    HIP_TRY(st.stamp("vertices posed"));
+    if (counters[0] != 0) {
+        return fail("%s: the posed position of %u vertices is not finite", who, counters[0]);
+    }
+    // (the counter is back and zero: from here on the live vertex array is written)
+    for (const StagedRange &r : staged) {
+        HIP_TRY(hipMemcpyAsync(c->vertices.as<rayhip_vertex>() + r.first, c->skin_stage.as<rayhip_vertex>() + r.at, size_t(r.count) * sizeof(rayhip_vertex),
+                               hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(st.stamp("vertices copied"));
+    return refit_after_vertices(c, st);
+}
+
+// skins alone: rayhip_scene_pose without morph sets, under its own name.  (It asks the context before it lets an empty call pass.)
+int rayhip_scene_pose_skins(rayhip_ctx *c, int n, const int *skins, const float *const *palettes) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (n < 0 || n > int(rayhip_skin::MAX_SKINS) || (n > 0 && (!skins || !palettes))) {
+        return fail("rayhip_scene_pose_skins: bad arguments");
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_scene_pose_skins")) {
+        return rc;
+    }
+    return pose_ranges(c, "rayhip_scene_pose_skins", "pose them together (rayhip_scene_pose)", 0, nullptr, nullptr, n, skins, palettes);
+}
+
+int rayhip_scene_pose(rayhip_ctx *c, int n_morphs, const int *morphs, const float *const *weights, int n_skins, const int *skins, const float *const *palettes) {
+    if (!c || use_device(c)) {
+        return 1;
+    }
+    if (n_morphs < 0 || n_morphs > int(rayhip_morph::MAX_MORPHS) || n_skins < 0 || n_skins > int(rayhip_skin::MAX_SKINS) ||
+        (n_morphs > 0 && (!morphs || !weights)) || (n_skins > 0 && (!skins || !palettes))) {
+        return fail("rayhip_scene_pose: bad arguments");
+    }
+    if (n_morphs == 0 && n_skins == 0) {
+        return 0;
+    }
+    if (const int rc = vertex_update_possible(c, "rayhip_scene_pose")) {
+        return rc;
+    }
+    return pose_ranges(c, "rayhip_scene_pose", "pose them together", n_morphs, morphs, weights, n_skins, skins, palettes);
 }
 
 // ---- the switch: vertex updates and poses may move triangle lights (light_refit.h) --------------------------------------------------
@@ -1295,24 +1184,10 @@ int rayhip_scene_refit_lights(rayhip_ctx *c, int on) {
         if (!lr.on) {
             return 0;
         }
-        for (const rayhip_ctx::Skin &k : c->skins) {
+        for (const auto &[r, noun] : c->vertex_ranges()) { // (skins, morph sets, normal sets)
             for (const auto &kept : c->refit.light_vertices) {
-                if (k.live && kept.first >= k.first && kept.first - k.first < k.count) {
-                    return fail("rayhip_scene_refit_lights: skin %d covers vertex %u of a triangle light; destroy it first", k.id, kept.first);
-                }
-            }
-        }
-        for (const rayhip_ctx::Morph &m : c->morphs) {
-            for (const auto &kept : c->refit.light_vertices) {
-                if (m.live && kept.first >= m.first && kept.first - m.first < m.count) {
-                    return fail("rayhip_scene_refit_lights: morph set %d covers vertex %u of a triangle light; destroy it first", m.id, kept.first);
-                }
-            }
-        }
-        for (const rayhip_ctx::Normals &n : c->normal_sets) {
-            for (const auto &kept : c->refit.light_vertices) {
-                if (n.live && kept.first >= n.first && kept.first - n.first < n.count) {
-                    return fail("rayhip_scene_refit_lights: normal set %d covers vertex %u of a triangle light; destroy it first", n.id, kept.first);
+                if (r->live && r->covers(kept.first)) {
+                    return fail("rayhip_scene_refit_lights: %s %d covers vertex %u of a triangle light; destroy it first", noun, r->id, kept.first);
                 }
             }
         }
@@ -1347,13 +1222,10 @@ int rayhip_scene_refit_lights(rayhip_ctx *c, int on) {
         std::vector<uint32_t> li(lr.li_count), vi(c->geometry.vtx_indices);
         std::vector<rayhip_vertex> vertices(c->geometry.vertices);
         std::vector<rayhip_mesh_instance> instances(c->instances_count);
-        auto back = [&](void *dst, const DevBuf &src, const size_t bytes) {
-            return bytes == 0 || hipMemcpy(dst, src.p, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-        };
-        if (!back(lights.data(), c->lights, lights.size() * sizeof(rayhip_light)) || !back(nodes.data(), c->light_cwnodes, nodes.size() * sizeof(rayhip_light_cwbvh_node)) ||
-            !back(li.data(), c->li_indices, li.size() * sizeof(uint32_t)) || !back(vi.data(), c->vtx_indices, vi.size() * sizeof(uint32_t)) ||
-            !back(vertices.data(), c->vertices, vertices.size() * sizeof(rayhip_vertex)) ||
-            !back(instances.data(), c->mesh_instances, instances.size() * sizeof(rayhip_mesh_instance))) {
+        if (!read_back(lights.data(), c->lights, lights.size() * sizeof(rayhip_light)) || !read_back(nodes.data(), c->light_cwnodes, nodes.size() * sizeof(rayhip_light_cwbvh_node)) ||
+            !read_back(li.data(), c->li_indices, li.size() * sizeof(uint32_t)) || !read_back(vi.data(), c->vtx_indices, vi.size() * sizeof(uint32_t)) ||
+            !read_back(vertices.data(), c->vertices, vertices.size() * sizeof(rayhip_vertex)) ||
+            !read_back(instances.data(), c->mesh_instances, instances.size() * sizeof(rayhip_mesh_instance))) {
             return fail("rayhip_scene_refit_lights: reading the scene back failed");
         }
         for (const auto &kept : c->refit.light_vertices) {

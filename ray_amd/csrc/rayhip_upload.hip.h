@@ -565,9 +565,9 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
     }
     const UploadTrace trace;
     trace("begin");
-    c->discard_skins(); // (a skin names a range of the vertex array this call replaces)
-    c->discard_morphs(); // (... and so does a morph set)
-    c->discard_normals(); // (... and a normal set, whose tables hold the topology besides)
+    c->skins.discard(); // (a skin names a range of the vertex array this call replaces)
+    c->morphs.discard(); // (... and so does a morph set)
+    c->normal_sets.discard(); // (... and a normal set, whose tables hold the topology besides)
     const rayhip_layout::AlignedDesc aligned(*d_in); // see bvh_layout.h
     const rayhip_scene_desc *d = &aligned.d;
     if (d->env.qtree_levels < 0 || d->env.qtree_levels > 16) {
