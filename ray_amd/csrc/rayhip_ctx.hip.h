@@ -322,6 +322,10 @@ struct rayhip_ctx {
     RaySoA record_rays = {};
     bool notex_kernels = true; // RAYHIP_NOTEX_KERNELS=0: scenes without textures take the general k_surface_scatter too
     bool pick_lds = true; // RAYHIP_PICK_LDS=0: the light pick reads every row of the light table from memory (shade_kernels.hip)
+    // RAYHIP_PICK_SPARSE=0: the light pick evaluates all eight children of every node (k_light_pick_first), not the occupied ones only
+    // (k_light_pick_sparse); RAYHIP_PICK_SPARSE_MAX_NODES lowers the node count up to which a scene takes the sparse form
+    bool pick_sparse = true;
+    uint32_t pick_sparse_max_nodes = 0xffffffffu;
     // RAYHIP_SHADE_LDS_TABLES=0: the shade kernels read the material / instance tables from memory, not from a copy in LDS (shade_kernels.hip);
     // RAYHIP_SHADE_LDS_MATERIALS_MAX / RAYHIP_SHADE_LDS_INSTANCES_MAX lower the counts up to which a scene takes the LDS form
     bool shade_lds_tables = true;
@@ -898,6 +902,12 @@ int rayhip_ctx_create(int device, rayhip_ctx **out_ctx) {
     }
     if (const char *e = getenv("RAYHIP_PICK_LDS")) {
         c->pick_lds = atoi(e) != 0;
+    }
+    if (const char *e = getenv("RAYHIP_PICK_SPARSE")) {
+        c->pick_sparse = atoi(e) != 0;
+    }
+    if (const char *e = getenv("RAYHIP_PICK_SPARSE_MAX_NODES")) {
+        c->pick_sparse_max_nodes = uint32_t(std::max(0, atoi(e)));
     }
     if (const char *e = getenv("RAYHIP_SURFACE_PARK")) {
         c->surface_park = atoi(e) != 0;

@@ -45,6 +45,7 @@ static void launch_shade(rayhip_ctx *c, const rayhip_camera &cam, int iteration,
     a.bounce = bounce, a.grid = gtrace, a.split = split >= 0 ? split : c->shade_split, a.stream = c->stream;
     a.picks = c->pick_plane.as<float4>(), a.record_rays = c->record_rays, a.tag = c->next_shade_tag();
     a.pick_lds = c->pick_lds, a.surface_park = c->surface_park;
+    a.pick_sparse = c->pick_sparse, a.pick_sparse_max_nodes = c->pick_sparse_max_nodes;
     a.lds_tables = c->shade_lds_tables, a.n_materials = c->geometry.materials, a.n_instances = c->instances_count;
     a.lds_materials_max = c->shade_lds_materials_max, a.lds_instances_max = c->shade_lds_instances_max;
     a.no_textures = c->textures_count == 0 && c->notex_kernels;

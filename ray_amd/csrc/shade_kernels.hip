@@ -490,6 +490,9 @@ __global__ void __launch_bounds__(WAVE, (NEE && CONTINUE) ? RT_SCATTER_MIN_WAVES
 // busy); the table of a scene with a few hundred lights is a few kilobytes.  A table that does not fit is read from memory as before (the
 // launcher picks the form; a kernel with both paths spills).
 // (7 waves: 72 registers, no spills; 8 spill 3-8 dwords: 16.4 against 16.8 ms per frame)
+// This kernel keeps the branch-free level (light_node_importances_rows: all eight children, occupied or not): its <.., false> form reads the
+// rows from memory, where a branch per child costs a round trip, and its <.., true> form is the fallback and the A/B partner
+// (RAYHIP_PICK_SPARSE=0) of k_light_pick_sparse below, which evaluates the occupied children only.
 #ifndef RT_PICK_LDS_MIN_WAVES
 #define RT_PICK_LDS_MIN_WAVES 7
 #endif
@@ -599,6 +602,184 @@ __global__ void __launch_bounds__(LDS_TREE ? PICK_BLOCK_WAVES *WAVE : WAVE, LDS_
 // on the refill path: 16.8 ms per frame against 16.3, at 80-100 registers.  The refill rounds are not what the kernel waits for; with the table
 // in LDS it is bound by the eight importance evaluations of a level -- nine quarter-rate reciprocals / square roots each.
 // profiles/r06/experiments/pick_lds_staged.txt; the kernel was removed.)
+
+// ---- the pick that evaluates only the occupied children of a node ---------------------------------------------------------------------
+// k_light_pick_first evaluates eight children per level, and the reference's light tree leaves most slots empty: it folds single-light leaves
+// into their parent and places children by Morton octant, so the atrium's 41 nodes hold 136 links in 328 slots.  Per level of that tree
+// (tools/light_tree_occupancy.py, profiles/pick_sparse): the root and its eight children are full, the 32 nodes below hold two lights each;
+// the asset street: full, full, 3.1 of 8.  With the rows in LDS a skipped child costs no round trip, so a lane can evaluate just the k-th
+// OCCUPIED child of its node, k = 0 .. K-1 with K the largest count among the wavefront's lanes (light_importance_of_occupied,
+// shade_lights.h: the unchanged light_child_importance on the same rows, its result put into imp[slot] by selects; then the unchanged
+// light_level_choice -- the same bits as the dense level).  That pays only where the lanes of a wavefront sit on nodes of like occupancy:
+// a lane that starts at the full root, or stands on one of its full children, keeps K at 8 for all.  So the lanes are not persistent
+// here.  A point between two levels waits in one of two stacks in LDS, by the occupancy of the node it is about to enter -- more than
+// PICK_SPARSE_FEW children ("many"), or at most that many ("few") -- and a round runs one level on up to 64 points of ONE kind and pushes
+// the survivors by their next node.  A round over many-children nodes is the branch-free level of k_light_pick_first (no selects to pay
+// for); a round over few-children nodes is the loop above.  A new chunk's points go into a round of the root's kind straight from their
+// loads, and the lanes of the chunk without a point (a miss, an emitter, the end of the queue) take one from that kind's stack.  A round
+// prefers a stack that fills the wavefront; when neither does and no chunk fits, a many-children round takes what both stacks hold (the
+// branch-free level is right for any node), so rounds with idle lanes happen only at the end.  The two stacks share one array per wavefront and grow towards each other: a round from the stacks never adds points,
+// a chunk is loaded only when 64 more fit, so they cannot meet.  (The order in which points are served is invisible: a pick is stored
+// under its ray's slot.)  What a point costs on top: two 16-byte LDS writes and reads per change of level.
+// Measured (MI355X, profiles/pick_sparse): 86.7 ms against k_light_pick_first's 98.7 over the benchmark's 6 frames (-12 %; the atrium's points
+// see ~2.5 levels, so ~18 % of the evaluations go), the headline from 815.7 to 826.1 Msamples/s (medians of three alternating runs each,
+// spreads 1.6 / 1.9), the same frame bits.  78-80 VGPRs, no scratch, 6 waves: three blocks per CU, which the LDS allows, too.
+// (A first form put every point through the stacks at every level, the chunk's included, seven dword planes each, and ran the loop over
+// occupied children on the full nodes too: 103.5 ms against k_light_pick_first's 98.2 over the benchmark's 6 frames -- profiles/pick_sparse.)
+#ifndef RT_PICK_SPARSE_MIN_WAVES
+#define RT_PICK_SPARSE_MIN_WAVES 6
+#endif
+#ifndef RT_PICK_SPARSE_FEW
+#define RT_PICK_SPARSE_FEW 4
+#endif
+constexpr uint32_t PICK_STACK_ENTRIES = 128u; // per wavefront, two float4 planes: (P, u) and (prob, node, ray slot, -)
+constexpr uint32_t PICK_STACK_BYTES = PICK_STACK_ENTRIES * 2u * 16u;
+constexpr uint32_t PICK_SPARSE_NODE_BYTES = uint32_t(LIGHT_CHILDREN_STRIDE) * 16u + uint32_t(sizeof(LightOccupancy));
+// dynamic LDS of a block: the rows, the occupancies (padded to a float4), the stacks
+constexpr uint32_t pick_sparse_occ_slots(const uint32_t nodes) { return (nodes + 1u) & ~1u; }
+constexpr size_t pick_sparse_lds_bytes(const uint32_t nodes) {
+    return size_t(nodes) * LIGHT_CHILDREN_STRIDE * 16u + size_t(pick_sparse_occ_slots(nodes)) * sizeof(LightOccupancy) + size_t(PICK_BLOCK_WAVES) * PICK_STACK_BYTES;
+}
+// RT_PICK_SPARSE_MIN_WAVES waves per SIMD are three blocks of eight wavefronts per CU (what k_light_pick_first<.., true> runs at with its
+// 72 registers, too): 46 nodes beside the eight stacks
+constexpr uint32_t PICK_SPARSE_LDS_PER_BLOCK = 160u * 1024u / (uint32_t(RT_PICK_SPARSE_MIN_WAVES) * 4u / uint32_t(PICK_BLOCK_WAVES)) - 2048u;
+constexpr uint32_t PICK_SPARSE_MAX_NODES = (PICK_SPARSE_LDS_PER_BLOCK - uint32_t(PICK_BLOCK_WAVES) * PICK_STACK_BYTES - uint32_t(sizeof(LightOccupancy))) / PICK_SPARSE_NODE_BYTES;
+static_assert(sizeof(LightOccupancy) == 8u && PICK_STACK_ENTRIES >= 2u * uint32_t(WAVE), "occupancy words behind the float4 rows; a chunk fits beside a full round");
+static_assert(pick_sparse_lds_bytes(PICK_SPARSE_MAX_NODES) <= PICK_SPARSE_LDS_PER_BLOCK && PICK_SPARSE_LDS_PER_BLOCK <= 64u * 1024u, "the cap fits; no opt-in for large LDS needed");
+struct PickEntry {
+    f3 P;
+    float u, prob;
+    uint32_t cur, i; // the node the point is about to enter; its ray slot
+};
+__device__ __forceinline__ void pick_entry_store(float4 *stack, const uint32_t at, const PickEntry &e) {
+    stack[at] = mkfloat4(e.P.x, e.P.y, e.P.z, e.u);
+    stack[PICK_STACK_ENTRIES + at] = mkfloat4(e.prob, uint_as_float(e.cur), uint_as_float(e.i), 0.0f);
+}
+__device__ __forceinline__ PickEntry pick_entry_load(const float4 *stack, const uint32_t at) {
+    const float4 a = stack[at], b = stack[PICK_STACK_ENTRIES + at];
+    PickEntry e;
+    e.P = f3{a.x, a.y, a.z}, e.u = a.w, e.prob = b.x, e.cur = float_as_uint(b.y), e.i = float_as_uint(b.z);
+    return e;
+}
+template <bool DYN>
+__global__ void __launch_bounds__(PICK_BLOCK_WAVES *WAVE, RT_PICK_SPARSE_MIN_WAVES) k_light_pick_sparse(const SceneView sc, const ShadeParams sp, const RaySoA rays_in, const HitSoA hits,
+                                                                              const RayQueue queue, float4 *__restrict__ picks, const uint32_t tag,
+                                                                              const Layering layers, uint32_t *__restrict__ work, const uint32_t lds_nodes) {
+    extern __shared__ float4 s_tree[]; // lds_nodes x LIGHT_CHILDREN_STRIDE rows | lds_nodes occupancies | PICK_BLOCK_WAVES stacks
+    const uint32_t n_rows = lds_nodes * uint32_t(LIGHT_CHILDREN_STRIDE);
+    for (uint32_t r = threadIdx.x; r < n_rows; r += blockDim.x) {
+        s_tree[r] = sc.light_children[r];
+    }
+    __syncthreads();
+    // derived here and not at upload: a light refit or a light pose rewrites rows on the device, and these follow them
+    LightOccupancy *s_occ = reinterpret_cast<LightOccupancy *>(s_tree + n_rows);
+    for (uint32_t n = threadIdx.x; n < lds_nodes; n += blockDim.x) {
+        s_occ[n] = light_node_occupancy(s_tree + n * uint32_t(LIGHT_CHILDREN_STRIDE));
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & uint32_t(WAVE - 1), wave = threadIdx.x / WAVE;
+    float4 *stack = reinterpret_cast<float4 *>(s_occ + pick_sparse_occ_slots(lds_nodes)) + wave * (2u * PICK_STACK_ENTRIES);
+    ChunkWalk walk(queue.live_chunks(), DYN ? work : nullptr, RT_PICK_RUN, blockIdx.x * uint32_t(PICK_BLOCK_WAVES) + wave, gridDim.x * uint32_t(PICK_BLOCK_WAVES));
+    const bool root_few = uint32_t(__builtin_amdgcn_readfirstlane(int(light_occupied_count(s_occ[0])))) <= uint32_t(RT_PICK_SPARSE_FEW);
+    // (uniform) points waiting in front of a node with many children: stack[0 .. n_many); with few: stack[PICK_STACK_ENTRIES - n_few ..)
+    uint32_t n_many = 0, n_few = 0;
+    bool exhausted = false; // (uniform) no chunk left to hand out
+    for (;;) {
+        bool few; // (uniform) the kind of this round
+        bool have = false;
+        PickEntry e;
+        e.P = f3{0.0f, 0.0f, 0.0f}, e.u = 0.0f, e.prob = 1.0f, e.cur = 0, e.i = 0;
+        if (n_few >= uint32_t(WAVE)) {
+            few = true;
+        } else if (n_many >= uint32_t(WAVE)) {
+            few = false;
+        } else if (!exhausted && n_many + n_few + uint32_t(WAVE) <= PICK_STACK_ENTRIES) {
+            // a new chunk: its points stand in front of the root
+            int found = 0;
+            uint32_t next_chunk, slot0 = 0, n_live = 0;
+            while (!found && walk.next(next_chunk)) { // (uniform)
+                uint32_t s, first, n;
+                found = __builtin_amdgcn_readfirstlane(int(queue.chunk(next_chunk, s, first, n)));
+                if (found) {
+                    slot0 = uint32_t(__builtin_amdgcn_readfirstlane(int(first)));
+                    n_live = uint32_t(__builtin_amdgcn_readfirstlane(int(n)));
+                }
+            }
+            if (!found) {
+                exhausted = true;
+                continue;
+            }
+            if (lane < n_live) {
+                e.i = slot0 + lane;
+                const float4 h = hits.oi_pi_t_u[e.i];
+                // a triangle was hit: as in k_light_pick_first
+                if (hits.v[e.i] >= 0.0f && float_as_int(h.x) >= 0) {
+                    const float4 o = rays_in.o_pdf[e.i], d = rays_in.d_cw[e.i];
+                    const uint2 xd = rays_in.xy_depth[e.i];
+                    const uint32_t layer = xy_layer(xd.x, layers);
+                    const ShadeParams spl = layer_params(sp, layer);
+                    e.P = f3{o.x, o.y, o.z} + h.z * f3{d.x, d.y, d.z}; // == ShadePoint::P (shade_point.h)
+                    e.u = light_pick_random(sc, spl, xy_real(xd.x, layers, layer), xd.y);
+                    have = true;
+                }
+            }
+            few = root_few;
+        } else if (n_many + n_few == 0u) {
+            break; // (and no chunk left: with both stacks empty a chunk would have fitted)
+        } else {
+            few = n_many == 0u; // neither stack fills a wavefront and no chunk fits (or none is left): the many-children kind, which takes the other along
+        }
+        // the lanes without a point take one from the stack of the round's kind; the lanes a round over many-children nodes still has
+        // free then take points of the other kind along (its level is right for any node, and costs the same with them)
+        for (int pass = 0; pass < (few ? 1 : 2); ++pass) {
+            const bool from_few = few || pass == 1;
+            const unsigned long long holes = __ballot(!have);
+            const uint32_t rank = uint32_t(__popcll(holes & ((1ull << lane) - 1ull)));
+            const uint32_t n_fill = min(uint32_t(__popcll(holes)), from_few ? n_few : n_many);
+            if (!have && rank < n_fill) {
+                e = pick_entry_load(stack, from_few ? PICK_STACK_ENTRIES - n_few + rank : n_many - 1u - rank);
+                have = true;
+            }
+            (from_few ? n_few : n_many) -= n_fill;
+        }
+        // one level (pick_light, shade_lights.h)
+        const float4 *rows = s_tree + e.cur * uint32_t(LIGHT_CHILDREN_STRIDE);
+        float imp[8];
+        if (few) {
+            const LightOccupancy occ = s_occ[e.cur];
+            const uint32_t n_occ = have ? light_occupied_count(occ) : 0u;
+            light_importances_preset(rows, occ, imp);
+            for (uint32_t k = 0; __ballot(k < n_occ) != 0ull; ++k) { // (uniform) the largest count among the lanes
+                if (k < n_occ) {
+                    light_importance_of_occupied(rows, occ, k, e.P, imp);
+                }
+            }
+        } else {
+            light_node_importances_rows(rows, e.P, imp); // (the lanes without a point: the root's rows at the origin, unused)
+        }
+        bool to_many = false, to_few = false;
+        if (have) {
+            int chosen;
+            if (light_level_choice(imp, e.u, e.prob, chosen)) { // false: nothing in this subtree can light P, no pick is written
+                e.cur = light_child_link_rows(rows, chosen);
+                if ((e.cur & LEAF_NODE_BIT) != 0) {
+                    picks[e.i] = mkfloat4(uint_as_float(e.cur & PRIM_INDEX_BITS), 1.0f / e.prob, e.u, uint_as_float(tag));
+                } else {
+                    to_few = light_occupied_count(s_occ[e.cur]) <= uint32_t(RT_PICK_SPARSE_FEW);
+                    to_many = !to_few;
+                }
+            }
+        }
+        const unsigned long long mask_many = __ballot(to_many), mask_few = __ballot(to_few);
+        if (to_many) {
+            pick_entry_store(stack, n_many + uint32_t(__popcll(mask_many & ((1ull << lane) - 1ull))), e);
+        }
+        if (to_few) {
+            pick_entry_store(stack, PICK_STACK_ENTRIES - 1u - (n_few + uint32_t(__popcll(mask_few & ((1ull << lane) - 1ull)))), e);
+        }
+        n_many += uint32_t(__popcll(mask_many)), n_few += uint32_t(__popcll(mask_few));
+    }
+}
 
 // TEX = false: the scene holds no texture (ShadeLaunch::no_textures): the surface stage without its lookups, RT_FUSED_NOTEX_MIN_WAVES
 #ifndef RT_FUSED_NOTEX_MIN_WAVES
@@ -851,7 +1032,9 @@ void launch(const ShadeLaunch &a) {
         const bool lights = a.sc.light_cwnodes_count != 0;
         if (lights) {
             const uint32_t lds_nodes = (a.pick_lds && a.sc.light_cwnodes_count <= PICK_LDS_MAX_NODES) ? a.sc.light_cwnodes_count : 0u;
-            auto go = [&](auto kernel, auto kernel_wave) {
+            // ... and only its occupied children evaluated (RAYHIP_PICK_SPARSE, default on), where the table and the stacks fit
+            const bool sparse = a.pick_sparse && lds_nodes != 0u && lds_nodes <= std::min(a.pick_sparse_max_nodes, PICK_SPARSE_MAX_NODES);
+            auto go = [&](auto kernel_sparse, auto kernel, auto kernel_wave) {
                 // (grids in wavefronts, from the one-wavefront form: the LDS form launches a quarter as many blocks of four)
                 int grid = sized(kernel_wave, a.expect[EXPECT_RAYS], all);
                 if (a.work) {
@@ -859,14 +1042,18 @@ void launch(const ShadeLaunch &a) {
                     const uint32_t bound = a.expect[EXPECT_RAYS] != 0u ? a.expect[EXPECT_RAYS] : a.chunks;
                     grid = int(std::max<uint32_t>(1u, std::min<uint32_t>({uint32_t(g), uint32_t(resident), std::max(bound, 1u)})));
                 }
-                if (lds_nodes != 0u) {
+                if (sparse) {
+                    kernel_sparse<<<(grid + PICK_BLOCK_WAVES - 1) / PICK_BLOCK_WAVES, PICK_BLOCK_WAVES * WAVE, pick_sparse_lds_bytes(lds_nodes), s>>>(
+                        a.sc, a.sp, a.rays_in, a.hits, a.in, a.picks, a.tag, a.layers, a.work, lds_nodes);
+                } else if (lds_nodes != 0u) {
                     kernel<<<(grid + PICK_BLOCK_WAVES - 1) / PICK_BLOCK_WAVES, PICK_BLOCK_WAVES * WAVE, size_t(lds_nodes) * LIGHT_CHILDREN_STRIDE * sizeof(float4), s>>>(
                         a.sc, a.sp, a.rays_in, a.hits, a.in, a.picks, a.tag, a.layers, a.work, lds_nodes);
                 } else {
                     kernel_wave<<<grid, WAVE, 0, s>>>(a.sc, a.sp, a.rays_in, a.hits, a.in, a.picks, a.tag, a.layers, a.work, 0u);
                 }
             };
-            a.work ? go(k_light_pick_first<true, true>, k_light_pick_first<true, false>) : go(k_light_pick_first<false, true>, k_light_pick_first<false, false>);
+            a.work ? go(k_light_pick_sparse<true>, k_light_pick_first<true, true>, k_light_pick_first<true, false>)
+                   : go(k_light_pick_sparse<false>, k_light_pick_first<false, true>, k_light_pick_first<false, false>);
         }
 #define RT_FUSED(...) k_surface_scatter<__VA_ARGS__><<<sized(k_surface_scatter<__VA_ARGS__>, a.expect[EXPECT_RAYS], all), WAVE, 0, s>>>( \
         a.sc, a.sp, a.rays_in, a.hits, a.in, a.picks, a.tag, a.points, a.record_rays, a.nee, a.rays_out, a.out_rays, a.deferred, a.out_deferred, a.px, a.vw, \

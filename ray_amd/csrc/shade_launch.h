@@ -47,6 +47,10 @@ struct ShadeLaunch {
     // planes + `record_rays` (direction | cone width, throughput | cone spread, ior stack, pixel | depth: the planes of a RaySoA, o_pdf unused)
     bool no_textures = false; // the uploaded scene holds no texture at all: k_surface_scatter without the lookups (shade_point.h: TEX)
     bool pick_lds = true; // k_light_pick_first keeps the top of the light table in LDS (RAYHIP_PICK_LDS=0: every row from memory)
+    // with the table in LDS: k_light_pick_sparse, which evaluates the occupied children of a node only, for a light tree of at most
+    // min(pick_sparse_max_nodes, the kernel's cap) nodes (RAYHIP_PICK_SPARSE=0: k_light_pick_first for every scene; RAYHIP_PICK_SPARSE_MAX_NODES)
+    bool pick_sparse = true;
+    uint32_t pick_sparse_max_nodes = 0xffffffffu;
     bool surface_park = true; // k_surface_scatter parks the ray in LDS across its stages (RAYHIP_SURFACE_PARK=0: the ray stays in registers)
     // round 8: k_surface_scatter (no-texture variants) and the next-event kernel read the material / instance tables from a copy in LDS when the
     // scene's counts (0: unknown -> never) are within the caps: the kernels' own (shade_kernels.hip: LDS_MATERIALS_MAX / LDS_INSTANCES_MAX), lowered

@@ -302,7 +302,10 @@ RT_HD float sin_of_clamped_difference(float sin_a, float cos_a, float sin_b, flo
 // (written without an early exit: an empty or box-less child yields its flux through the final select, the arithmetic above it
 // runs on the zero rows of its table entry and is discarded.  That keeps the eight evaluations of a node free of control
 // flow, so the compiler can issue the table loads of all children before the first use -- with the branch the descent
-// paid one memory round trip per child, 8 in a row per level, and k_light_pick sat 75 % of its time in s_waitcnt.)
+// paid one memory round trip per child, 8 in a row per level, and k_light_pick sat 75 % of its time in s_waitcnt.
+// The kernels that read the rows from MEMORY still want this form: pick_light, k_light_pick, k_light_pick_refill and
+// k_light_pick_first.  k_light_pick_sparse reads them from LDS, where a skipped child costs no round trip: it calls this
+// function for the children that need the arithmetic only, light_node_importances_sparse below.)
 RT_HD float light_child_importance(const LightChild &c, const f3 P) {
     const float flux = c.cosines.w;
     const float half_diag = c.axis_extent.w;
@@ -341,6 +344,63 @@ RT_HD void light_node_importances_rows(const float4 *node_rows, const f3 P, floa
     }
     for (int i = 0; i < 8; ++i) {
         imp[i] = light_child_importance(c[i], P);
+    }
+}
+// ---- the same eight importances, evaluated for the occupied children only ---------------------------------------------------
+// Which children of a node need the arithmetic of light_child_importance: exactly the condition of its final select.  Every
+// other child's importance is its cosines.w as it stands -- 0 for an empty slot, the flux of a box-less light (directional),
+// 0 for an emitter without flux.  Derived from the rows (not at upload): light_refit.hip.h and light_pose.hip.h rewrite rows
+// on the device, and what is derived where the rows are read follows them.
+struct LightOccupancy {
+    uint32_t masks; // bits 0-7: children that need the arithmetic; 8-15: the others whose cosines.w is not +0; 16-19: how many of the first
+    uint32_t slots; // the slot numbers of the first kind in ascending order, four bits each
+};
+RT_HD LightOccupancy light_node_occupancy(const float4 *node_rows) {
+    LightOccupancy o;
+    o.masks = 0u, o.slots = 0u;
+    uint32_t count = 0u;
+    for (int i = 0; i < 8; ++i) {
+        const float valid = node_rows[2 + 1 * 8 + i].w, flux = node_rows[2 + 2 * 8 + i].w;
+        if (valid != 0.0f && flux != 0.0f) {
+            o.masks |= 1u << i;
+            o.slots |= uint32_t(i) << (4u * count);
+            ++count;
+        } else if (float_as_uint(flux) != 0u) {
+            o.masks |= 0x100u << i;
+        }
+    }
+    o.masks |= count << 16;
+    return o;
+}
+RT_HD uint32_t light_occupied_count(const LightOccupancy &o) { return o.masks >> 16; }
+// imp[] of the children that need no arithmetic (all of it is written)
+RT_HD void light_importances_preset(const float4 *node_rows, const LightOccupancy &o, float imp[8]) {
+    for (int j = 0; j < 8; ++j) {
+        imp[j] = 0.0f;
+    }
+    if ((o.masks & 0xff00u) != 0u) { // (rare: a node with a directional light below it, or a flux of -0)
+        for (int j = 0; j < 8; ++j) {
+            if ((o.masks & (0x100u << j)) != 0u) {
+                imp[j] = node_rows[2 + 2 * 8 + j].w;
+            }
+        }
+    }
+}
+// the k-th occupied child (k < light_occupied_count): its importance goes to its slot of imp[] through a chain of selects -- an
+// indexed local array would live in scratch
+RT_HD void light_importance_of_occupied(const float4 *node_rows, const LightOccupancy &o, const uint32_t k, const f3 P, float imp[8]) {
+    const int slot = int((o.slots >> (4u * k)) & 7u);
+    const float v = light_child_importance(load_light_child_rows(node_rows, slot), P);
+    for (int j = 0; j < 8; ++j) {
+        imp[j] = (slot == j) ? v : imp[j];
+    }
+}
+// one lane's form of the sparse level (the host build and the tests; k_light_pick_sparse runs the loop wavefront-wide): the same
+// operands through the same function as light_node_importances_rows, hence the same bits in every imp[j]
+RT_HD void light_node_importances_sparse(const float4 *node_rows, const LightOccupancy &o, const f3 P, float imp[8]) {
+    light_importances_preset(node_rows, o, imp);
+    for (uint32_t k = 0; k < light_occupied_count(o); ++k) {
+        light_importance_of_occupied(node_rows, o, k, P, imp);
     }
 }
 RT_HD float sum8_sse_order(const float v[8]) { return (((v[0] + v[4]) + (v[1] + v[5])) + (v[2] + v[6])) + (v[3] + v[7]); }
