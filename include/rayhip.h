@@ -381,8 +381,11 @@ RAYHIP_API int rayhip_scene_upload(rayhip_ctx *ctx, const rayhip_scene_desc *des
  * the live instance slots and their world-space boxes), visible/blocker light counts and bounds are used, vertices /
  * vtx_indices for the corners of triangle lights; textures / texels may be null.  The top-level tree is rebuilt on the
  * device over those boxes (ray_amd/csrc/lbvh.hip.h).  Meshes, materials and textures must be the ones of the last
- * rayhip_scene_upload.  Returns 0; 1 = error; 2 = this change needs rayhip_scene_upload (an instance of a mesh that was
- * not in use at the last upload, geometry arrays of another size) -- nothing on the device was touched.  After 1 the
+ * rayhip_scene_upload: the materials that are on the device stay -- those rayhip_scene_set_materials wrote too -- while the
+ * lights are the host's, the colours its emissive materials gave them included (see there).  tri_materials and materials
+ * are read for the emitters of the triangle lights.  Returns 0; 1 = error; 2 = this change needs rayhip_scene_upload
+ * (an instance of a mesh that was not in use at the last upload, geometry arrays of another size) -- nothing on the
+ * device was touched.  After 1 the
  * context still holds the previous top-level tree (new trees are written to alternating halves of a reserved region),
  * but instance / light arrays may already be the new ones: re-send the scene with rayhip_scene_upload. */
 RAYHIP_API int rayhip_scene_update_instances(rayhip_ctx *ctx, const rayhip_scene_desc *desc);
@@ -595,12 +598,38 @@ RAYHIP_API int rayhip_scene_set_lights(rayhip_ctx *ctx, uint32_t n, const uint32
  * that is 16-byte aligned is read with 16-byte loads; it must be 4-byte aligned. */
 RAYHIP_API int rayhip_scene_set_lights_device(rayhip_ctx *ctx, uint32_t n, const uint32_t *device_slots, const rayhip_light *device_records);
 
+/* MATERIALS THAT CHANGE (a colour that fades, a roughness that ramps, two materials cross-faded through a Mix node's factor, a glowing
+ * mesh that dims or changes colour): new records for n material slots of the uploaded scene, and nothing else -- no host scene, no
+ * rayhip_scene_desc (ray_amd/csrc/materials.h, materials.hip.h).  records[i] is a complete rayhip_material, the layout of
+ * rayhip_scene_desc::materials, and replaces material slot slots[i]: base_color, tangent_rotation_or_strength, ior and the eleven
+ * *_unorm halves may change; textures[5], flags and type must be bytewise the words the slot holds -- two of a Mix node's textures are
+ * its operands, so the node graph stays, and with it what an upload derives from the materials: the solid bits of the triangles, the
+ * choice of kernels, the validity of the texture handles, which triangle light has which emitter.  Where a named material is the
+ * emitter of triangle lights (the scene build bakes the first importance-sampled Emissive material found breadth-first from a
+ * triangle's front material through its Mix operands into the light: col = base_color * strength), those lights take the new colour,
+ * their leaf summaries the new flux, and the light tree and its importance rows are refitted as after a vertex update, all before the
+ * call returns; a call that names no emitter leaves the light arrays alone.  It waits for pending passes first; the accumulated image
+ * is the caller's to clear.  Everything is checked before anything on the device is written -- a refused call has touched nothing.
+ * Returns 0; 1 = a null pointer with n > 0, a slot outside the material array or one that no reachable triangle and no Mix operand
+ * uses, a slot named twice, a changed type, flags or texture word, a float that is not finite, a negative base_color component or
+ * strength of an Emissive record; 2 = the scene needs rayhip_scene_upload: there is none, a record refracts (Refractive, or Principled
+ * with transmission) while the uploaded scene had no such surface and its passes do not carry the rays' ior stacks (the reverse
+ * passes), or a named emitter's base_color or strength would change while rayhip_scene_refit_lights is off or its tables are not
+ * prepared (a bytewise unchanged colour and strength passes).  n == 0 returns 0 and launches nothing.
+ * A later rayhip_scene_update_instances keeps the DEVICE's materials but brings the HOST's lights, colours included: a caller who
+ * recoloured emitters keeps the materials of their host scene in step, or names those materials again afterwards (with the switch on
+ * the lights of every named emitter are recoloured, changed or not). */
+RAYHIP_API int rayhip_scene_set_materials(rayhip_ctx *ctx, uint32_t n, const uint32_t *slots, const rayhip_material *records);
+/* the same from DEVICE memory of the context's device, complete when the call is made and unchanged until it returns; 4-byte aligned. */
+RAYHIP_API int rayhip_scene_set_materials_device(rayhip_ctx *ctx, uint32_t n, const uint32_t *device_slots, const rayhip_material *device_records);
+
 /* test hook: copy a device array of the acceleration structure to the host. which: 0 BVH2 nodes [0, nodes_used),
  * 1 tris as 48-byte records (un-pitched), 2 tri_indices, 3 the live top-level leaves as (instance slot, lo.xyz, hi.xyz) 7 x 4 bytes each,
  * 4 the vertex array as 44-byte records, 5 the light tree (light_cwnodes, 208 bytes each), 6 its importance rows (light_children,
  * 26 x 16 bytes per node), 7 the world-space corners of the triangle lights (light_tri_geom, 4 x 16 bytes per light slot),
  * 8 the instance array (144 bytes per slot), 9 the light array (64 bytes per slot), 10 the leaf summaries of the light refit (48 bytes
- * per light slot: box lo / hi, flux, cone axis, omega_n, omega_e; needs rayhip_scene_refit_lights) */
+ * per light slot: box lo / hi, flux, cone axis, omega_n, omega_e; needs rayhip_scene_refit_lights), 11 the material array (76 bytes
+ * per slot) */
 RAYHIP_API int rayhip_k_read_accel(rayhip_ctx *ctx, int which, void *dst, size_t capacity_bytes, size_t *out_bytes);
 
 /* 1024-entry inverse filter CDF (RendererCPU.h:1234-1258 UpdateFilterTable; upload RendererVK.cpp:386-424) */

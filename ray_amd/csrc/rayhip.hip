@@ -36,6 +36,7 @@
 #include "normals.hip.h"
 #include "light_refit.hip.h"
 #include "light_pose.hip.h"
+#include "materials.hip.h"
 #include "instances.hip.h"
 #include "scene_blob.h"
 #include "scene_rebuild.h"

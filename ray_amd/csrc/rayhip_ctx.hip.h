@@ -190,6 +190,15 @@ struct rayhip_ctx {
         DevBuf live, posed, claim;
     } light_refit;
     DevBuf light_stage, light_args, light_counters; // rayhip_scene_set_lights: staged records, summaries and slots; the caller's arrays; the findings
+    // what rayhip_scene_set_materials checks its slots against (materials.h): per material slot SLOT_LIVE (the upload's validation: a
+    // reachable triangle or a Mix operand uses it) | SLOT_EMITTER (some triangle light took its colour from it), on the host and on the
+    // device, one claim word per slot, and per light slot the material it took its colour from.  The emitters are found again by an
+    // instance update, which replaces the lights.
+    struct MaterialChecks {
+        std::vector<uint8_t> flags;
+        DevBuf d_flags, d_claim, d_light_emitter;
+    } material_checks;
+    DevBuf material_stage, material_args, material_counters; // rayhip_scene_set_materials: staged records and slots; the caller's arrays; the counters
     // ---- handles over vertex ranges: skins, morph sets and normal sets.  A record of any kind begins with the same head ...
     struct RangeHead {
         bool live = false;
@@ -1000,7 +1009,8 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
                       &c->light_refit.level_nodes, &c->light_refit.leaf, &c->light_refit.node_summary, &c->light_refit.slot_scale, &c->skin_stage,
                       &c->skin_palettes, &c->skin_counters, &c->refit.d_slot_flags, &c->refit.d_live, &c->refit.d_slot_claim, &c->instance_stage,
                       &c->instance_args, &c->instance_counters, &c->light_refit.live, &c->light_refit.posed, &c->light_refit.claim, &c->light_stage,
-                      &c->light_args, &c->light_counters}) {
+                      &c->light_args, &c->light_counters, &c->material_checks.d_flags, &c->material_checks.d_claim, &c->material_checks.d_light_emitter,
+                      &c->material_stage, &c->material_args, &c->material_counters}) {
         b->release();
     }
     for (hipEvent_t e : c->events) {

@@ -1,13 +1,14 @@
 // rayhip_deform.hip.h -- part of librayhip's host side (one translation unit: included by rayhip.hip before rayhip_upload.hip.h):
 // deforming a scene that is on the device.  In reading order:
 //   - the tables an upload or instance update leaves behind (prepare_refit, keep_light_vertices, upload_vertex_checks,
-//     upload_instance_checks, prepare_light_refit);
+//     upload_instance_checks, upload_material_checks, prepare_light_refit);
 //   - what the entry points share: the phase stamps, the preconditions, the launch grid, the read-back;
 //   - the light refit and the geometry refit behind new vertices, and the top level behind either;
 //   - the vertex updates (rayhip_scene_update_vertices, its _blob and _device forms; refit.h);
 //   - the calls that take slots and records, each from host or device memory: the instances that move
-//     (rayhip_scene_set_instance_transforms[_device]; instances.h) and the analytic lights that move or change colour
-//     (rayhip_scene_set_lights[_device]; light_pose.h);
+//     (rayhip_scene_set_instance_transforms[_device]; instances.h), the analytic lights that move or change colour
+//     (rayhip_scene_set_lights[_device]; light_pose.h) and the materials that change, with the triangle lights they colour
+//     (rayhip_scene_set_materials[_device]; materials.h);
 //   - the handles over vertex ranges: skins (rayhip_skin_create / _destroy; skin.h), morph sets (rayhip_morph_create / _destroy;
 //     morph.h) and normal sets (rayhip_normals_create / _destroy; normals.h: recomputed at the top of the geometry refit);
 //   - the poses (rayhip_scene_pose, and rayhip_scene_pose_skins, which is the same without morph sets);
@@ -137,6 +138,34 @@ static int upload_instance_checks(rayhip_ctx *c, const rayhip_scene_desc *d) {
         r.d_slot_claim.alloc(r.slot_flags.size() * sizeof(uint32_t)) || hipStreamSynchronize(c->stream) != hipSuccess) {
         r.slot_flags.clear(); // (no table on the device: a call that moves instances says that it needs an upload)
         return fail("the per-slot table of the instances could not be uploaded");
+    }
+    return 0;
+}
+
+// ... and what a call that changes materials checks its slots against (rayhip_scene_set_materials; materials.h, k_check_materials): per
+// material slot whether the scene uses it and whether a triangle light took its colour from it, on the host and on the device, one
+// claim word per slot, and per light slot its emitter (k_recolour_tri_lights).  `d`: the light arrays, tri_materials and materials;
+// `used`: the validation's per-slot bytes (an upload), or null: the slots in use stay (an instance update names no mesh the upload
+// did not bring) and only the emitters are found again, by the graph of `d`'s materials
+static int upload_material_checks(rayhip_ctx *c, const rayhip_scene_desc *d, const std::vector<uint8_t> *used) {
+    namespace rm = rayhip_materials;
+    rayhip_ctx::MaterialChecks &mc = c->material_checks;
+    if (used) {
+        mc.flags.assign(d->materials_count, 0);
+        for (size_t m = 0; m < mc.flags.size() && m < used->size(); ++m) {
+            mc.flags[m] = (*used)[m] ? uint8_t(rm::SLOT_LIVE) : uint8_t(0);
+        }
+    } else if (mc.flags.size() != d->materials_count) { // (an upload that failed half-way: nothing to keep)
+        mc.flags.clear();
+        return 0;
+    }
+    std::vector<uint16_t> light_emitter;
+    rm::emitter_tables(d->lights, d->lights_count, d->li_indices, d->li_indices_count, d->tri_materials, d->tri_materials_count, d->materials, d->materials_count,
+                       light_emitter, mc.flags);
+    if (upload(c, mc.d_flags, mc.flags.data(), mc.flags.size()) || upload(c, mc.d_light_emitter, light_emitter.data(), light_emitter.size() * sizeof(uint16_t)) ||
+        mc.d_claim.alloc(mc.flags.size() * sizeof(uint32_t)) || hipStreamSynchronize(c->stream) != hipSuccess) {
+        mc.flags.clear(); // (no table on the device: a call that changes materials says that it needs an upload)
+        return fail("the per-slot table of the materials could not be uploaded");
     }
     return 0;
 }
@@ -556,12 +585,13 @@ int rayhip_scene_update_vertices_device(rayhip_ctx *c, uint32_t first_vertex, ui
     return refit_after_vertices(c, st);
 }
 
-// ---- calls that take slots and records: n slots of an array on the device and n records of 64 bytes for them --------------------------
+// ---- calls that take slots and records: n slots of an array on the device and n records of RecordBytes for them -----------------------
 // What the host and the device form of such a call do around its body.  `possible`: the preconditions, asked first; an empty call that
 // passes them returns 0 with nothing touched.  `host_args`: the context's buffer that takes a copy of the caller's HOST arrays, [n]
 // records then [n] slots; null: `slots` and `records` are device memory, complete and stable until the call returns, and go to the
-// body as they are.  (The body waits for the stream before it returns: host arrays may go away then.)
-extern "C++" template <typename Record>
+// body as they are.  (The body waits for the stream before it returns: host arrays may go away then.)  RecordBytes: a multiple of 4 --
+// the size of Record, but for a record that is passed as its first float (a transform: sixteen).
+extern "C++" template <typename Record, size_t RecordBytes = sizeof(Record)>
 static int set_records(rayhip_ctx *c, const char *who, const uint32_t n, const uint32_t *slots, const Record *records, DevBuf rayhip_ctx::*host_args,
                        int (*possible)(rayhip_ctx *, const char *, uint32_t, const void *, const void *),
                        int (*body)(rayhip_ctx *, const VertexStamps &, uint32_t, const uint32_t *, const Record *)) {
@@ -581,12 +611,13 @@ static int set_records(rayhip_ctx *c, const char *who, const uint32_t n, const u
         return body(c, st, n, slots, records);
     }
     DevBuf &args = c->*host_args;
-    if (args.alloc(size_t(n) * 68)) {
+    static_assert(RecordBytes % 4 == 0, "the slots lie behind the records");
+    if (args.alloc(size_t(n) * (RecordBytes + 4))) {
         return 1;
     }
     Record *d_records = args.as<Record>();
-    uint32_t *d_slots = reinterpret_cast<uint32_t *>(args.as<uint8_t>() + size_t(n) * 64);
-    HIP_TRY(hipMemcpyAsync(d_records, records, size_t(n) * 64, hipMemcpyHostToDevice, c->stream));
+    uint32_t *d_slots = reinterpret_cast<uint32_t *>(args.as<uint8_t>() + size_t(n) * RecordBytes);
+    HIP_TRY(hipMemcpyAsync(d_records, records, size_t(n) * RecordBytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_slots, slots, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
     return body(c, st, n, d_slots, d_records);
 }
@@ -690,11 +721,11 @@ static int instance_move_possible(rayhip_ctx *c, const char *who, const uint32_t
 }
 
 int rayhip_scene_set_instance_transforms(rayhip_ctx *c, uint32_t n, const uint32_t *slots, const float *xforms) {
-    return set_records(c, "rayhip_scene_set_instance_transforms", n, slots, xforms, &rayhip_ctx::instance_args, instance_move_possible, set_instance_transforms);
+    return set_records<float, 64>(c, "rayhip_scene_set_instance_transforms", n, slots, xforms, &rayhip_ctx::instance_args, instance_move_possible, set_instance_transforms);
 }
 
 int rayhip_scene_set_instance_transforms_device(rayhip_ctx *c, uint32_t n, const uint32_t *device_slots, const float *device_xforms) {
-    return set_records(c, "rayhip_scene_set_instance_transforms_device", n, device_slots, device_xforms, nullptr, instance_move_possible, set_instance_transforms);
+    return set_records<float, 64>(c, "rayhip_scene_set_instance_transforms_device", n, device_slots, device_xforms, nullptr, instance_move_possible, set_instance_transforms);
 }
 
 // ---- analytic lights that move or change colour: records in, leaf summaries on the device, the light tree refitted (light_pose.h) ----
@@ -784,6 +815,101 @@ int rayhip_scene_set_lights(rayhip_ctx *c, uint32_t n, const uint32_t *slots, co
 
 int rayhip_scene_set_lights_device(rayhip_ctx *c, uint32_t n, const uint32_t *device_slots, const rayhip_light *device_records) {
     return set_records(c, "rayhip_scene_set_lights_device", n, device_slots, device_records, nullptr, light_move_possible, set_lights);
+}
+
+// ---- materials that change: records in, the triangle lights they colour recoloured, the light tree refitted (materials.h) ------------
+// The node graph stays (type, flags, textures), so everything an upload derives from the materials stays valid.  k_check_materials
+// stages the new records and counts what is wrong with the call; only when its counters came back clean are the records scattered into
+// the material array (k_commit_materials).  Where a named material is the emitter of triangle lights -- whether its colour changed or
+// not: an instance update may have brought other colours since -- the lights take base_color * strength of the committed record
+// (k_recolour_tri_lights) and the light refit runs as it is behind a vertex update: summaries with the new flux, then the level
+// launches.  A call that names no emitter launches nothing over the light arrays.  Bound by its launches and its one read-back.
+// `d_slots` / `d_records`: device memory, complete and stable until the call returns, 4-byte aligned.
+static int set_materials(rayhip_ctx *c, const VertexStamps &st, const uint32_t n, const uint32_t *d_slots, const rayhip_material *d_records) {
+    namespace rm = rayhip_materials;
+    rayhip_ctx::MaterialChecks &mc = c->material_checks;
+    rayhip_ctx::LightRefit &lr = c->light_refit;
+    hipStream_t s = c->stream;
+    const uint32_t n_materials = c->geometry.materials;
+    // one block: [n] staged records of 76 bytes, [n] slots
+    const size_t slots_at = size_t(n) * sizeof(rayhip_material);
+    if (c->material_stage.alloc(slots_at + size_t(n) * 4) || c->material_counters.alloc(16 * sizeof(uint32_t))) {
+        return 1;
+    }
+    uint32_t *d_staged = c->material_stage.as<uint32_t>();
+    uint32_t *d_staged_slots = reinterpret_cast<uint32_t *>(c->material_stage.as<uint8_t>() + slots_at);
+    uint32_t *d_counters = c->material_counters.as<uint32_t>(); // ([N_COUNTERS]: triangle lights without area)
+    const bool refittable = lr.on && lr.ready;
+    HIP_TRY(hipMemsetAsync(d_counters, 0, 16 * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(mc.d_claim.p, 0, size_t(n_materials) * sizeof(uint32_t), s));
+    rm::k_check_materials<<<blocks_of(n), 256, 0, s>>>(d_slots, reinterpret_cast<const uint32_t *>(d_records), n, c->materials.as<rayhip_material>(), n_materials,
+                                                       mc.d_flags.as<uint8_t>(), mc.d_claim.as<uint32_t>(), c->plain_ior, refittable, d_staged, d_staged_slots,
+                                                       d_counters);
+    HIP_TRY(hipGetLastError());
+    uint32_t counters[rm::N_COUNTERS] = {};
+    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(st.stamp("materials checked"));
+    if (counters[rm::BAD_SLOT] != 0) {
+        return fail("%s: %u of the slots are outside the %u material slots, or used by no triangle of the scene", st.who, counters[rm::BAD_SLOT], n_materials);
+    }
+    if (counters[rm::DUPLICATE] != 0) {
+        return fail("%s: %u slots are named more than once", st.who, counters[rm::DUPLICATE]);
+    }
+    if (counters[rm::GRAPH_CHANGED] != 0) {
+        return fail("%s: type, flags or a texture word of %u records differ from those the slot holds", st.who, counters[rm::GRAPH_CHANGED]);
+    }
+    if (counters[rm::NOT_FINITE] != 0) {
+        return fail("%s: %u records have a colour, a strength or an ior that is not finite", st.who, counters[rm::NOT_FINITE]);
+    }
+    if (counters[rm::NEGATIVE] != 0) {
+        return fail("%s: %u emissive records have a negative colour or strength", st.who, counters[rm::NEGATIVE]);
+    }
+    if (counters[rm::REFRACTS] != 0) {
+        (void)fail("%s: %u records refract, and the uploaded scene had no refractive surface: its passes do not carry the rays' ior stacks", st.who,
+                   counters[rm::REFRACTS]);
+        return 2;
+    }
+    if (counters[rm::PINNED] != 0) {
+        (void)fail("%s: %u of the materials colour triangle lights; lights are not rebuilt by this call (rayhip_scene_refit_lights)", st.who, counters[rm::PINNED]);
+        return 2;
+    }
+    // (the counters are back and clean: from here on the live material array is written)
+    rm::k_commit_materials<<<blocks_of(size_t(n) * rm::RECORD_WORDS), 256, 0, s>>>(d_staged, d_staged_slots, n, c->materials.as<uint32_t>(), n_materials);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(st.stamp("materials committed"));
+    if (counters[rm::EMITTERS_NAMED] != 0 && refittable && lr.lights_count != 0) {
+        rm::k_recolour_tri_lights<<<blocks_of(lr.lights_count), 256, 0, s>>>(c->lights.as<rayhip_light>(), lr.lights_count, mc.d_light_emitter.as<uint16_t>(),
+                                                                             mc.d_claim.as<uint32_t>(), c->materials.as<rayhip_material>(), n_materials);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(st.stamp("lights recoloured"));
+        if (refit_lights(c, d_counters + rm::N_COUNTERS, st)) {
+            return 1;
+        }
+        HIP_TRY(hipMemcpyAsync(&lr.degenerate, d_counters + rm::N_COUNTERS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+// what both forms check before anything else: 0 = go on, 1 / 2 = the return code
+static int material_change_possible(rayhip_ctx *c, const char *who, const uint32_t n, const void *slots, const void *records) {
+    if (const int rc = scene_change_possible(c, who, n > 0 && (!slots || !records), false)) { // (no tree of the geometry is rebuilt)
+        return rc;
+    }
+    if (c->material_checks.flags.size() != c->geometry.materials) { // (an upload that failed half-way)
+        (void)fail("%s: the tables of the last upload are incomplete", who);
+        return 2;
+    }
+    return 0;
+}
+
+int rayhip_scene_set_materials(rayhip_ctx *c, uint32_t n, const uint32_t *slots, const rayhip_material *records) {
+    return set_records(c, "rayhip_scene_set_materials", n, slots, records, &rayhip_ctx::material_args, material_change_possible, set_materials);
+}
+
+int rayhip_scene_set_materials_device(rayhip_ctx *c, uint32_t n, const uint32_t *device_slots, const rayhip_material *device_records) {
+    return set_records(c, "rayhip_scene_set_materials_device", n, device_slots, device_records, nullptr, material_change_possible, set_materials);
 }
 
 // ---- handles over vertex ranges: what creating and destroying a skin, a morph set and a normal set share ----------------------------

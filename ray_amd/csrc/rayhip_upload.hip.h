@@ -579,9 +579,10 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
         return 1;
     }
     bool all_sides_solid = false; // (over the triangles the trees reach: the pools are sparse, an unused slot is all zeros)
+    std::vector<uint8_t> materials_used; // (... and the material slots they use: what rayhip_scene_set_materials may name)
     { // every index a kernel would follow without a bound of its own (scene_validate.h)
         std::string why;
-        if (!rayhip_validate::validate(*d, why, &all_sides_solid)) {
+        if (!rayhip_validate::validate(*d, why, &all_sides_solid, &materials_used)) {
             return fail("%s", why.c_str());
         }
     }
@@ -611,7 +612,7 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
         return 1;
     }
     keep_light_vertices(c, d); // (... and what a vertex update checks against them: rayhip_deform.hip.h)
-    if (upload_vertex_checks(c, true) || upload_instance_checks(c, d)) {
+    if (upload_vertex_checks(c, true) || upload_instance_checks(c, d) || upload_material_checks(c, d, &materials_used)) {
         return 1;
     }
     trace("lights done");
@@ -747,6 +748,12 @@ int rayhip_scene_update_instances(rayhip_ctx *c, const rayhip_scene_desc *d) {
     c->refit.live = live, c->refit.instances = mis; // (what a later rayhip_scene_update_vertices rebuilds the top level over, and the direct entry's source)
     refresh_scene_view(c, d, tlas_root, root_box, uint32_t(live.size()));
     if (upload_instance_checks(c, d)) { // (... and what a later rayhip_scene_set_instance_transforms checks its slots against)
+        return 1;
+    }
+    // ... and the emitters of the lights just brought (materials.h); without the arrays to find them in, rayhip_scene_set_materials needs an upload
+    if (!d->tri_materials || !d->materials) {
+        c->material_checks.flags.clear();
+    } else if (upload_material_checks(c, d, nullptr)) {
         return 1;
     }
     trace("instances updated");
@@ -886,6 +893,8 @@ int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_byt
             return fail("rayhip_k_read_accel: array 10 needs rayhip_scene_refit_lights");
         }
         src = c->light_refit.leaf.p, bytes = size_t(c->light_refit.lights_count) * sizeof(rayhip_light_refit::Summary);
+    } else if (which == 11) {
+        src = c->materials.p, bytes = size_t(c->geometry.materials) * sizeof(rayhip_material);
     } else {
         return fail("rayhip_k_read_accel: no array %d", which);
     }

@@ -69,8 +69,9 @@ inline bool validate_lights(const rayhip_scene_desc &d, std::string &err);
 inline bool validate_sky(const rayhip_scene_desc &d, std::string &err);
 
 // `all_sides_solid` (optional): is every side of every REACHABLE triangle plainly solid?  (the triangle pool is sparse: unused slots hold
-// zeros, which would read as "not solid")
-inline bool validate(const rayhip_scene_desc &d, std::string &err, bool *all_sides_solid = nullptr) {
+// zeros, which would read as "not solid").  `materials_used` (optional): one byte per material slot, 1 where a reachable triangle or a Mix
+// operand uses it -- the slots rayhip_scene_set_materials may name (materials.h)
+inline bool validate(const rayhip_scene_desc &d, std::string &err, bool *all_sides_solid = nullptr, std::vector<uint8_t> *materials_used = nullptr) {
     if (!validate_sky(d, err)) {
         return false;
     }
@@ -234,6 +235,9 @@ inline bool validate(const rayhip_scene_desc &d, std::string &err, bool *all_sid
                 return fail(err, "texture mip end", t, end, uint64_t(d.texels_count) + 1);
             }
         }
+    }
+    if (materials_used) {
+        *materials_used = mat_used;
     }
     return validate_lights(d, err);
 }

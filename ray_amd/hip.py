@@ -116,11 +116,17 @@ assert LIGHT_NODE_DTYPE.itemsize == 208
 MESH_INSTANCE_DTYPE = np.dtype([("mesh_index", "<u4"), ("node_index", "<u4"), ("lights_index", "<u4"), ("ray_visibility", "<u4"),
                                 ("xform", "<f4", 16), ("inv_xform", "<f4", 16)])  # rayhip_mesh_instance
 assert MESH_INSTANCE_DTYPE.itemsize == 144
+MATERIAL_DTYPE = np.dtype([("textures", "<u4", 5), ("base_color", "<f4", 3), ("flags", "<u4"), ("type", "<u4"), ("tangent_rotation_or_strength", "<f4"),
+                           ("roughness_unorm", "<u2"), ("anisotropic_unorm", "<u2"), ("ior", "<f4"), ("sheen_unorm", "<u2"), ("sheen_tint_unorm", "<u2"),
+                           ("tint_unorm", "<u2"), ("metallic_unorm", "<u2"), ("transmission_unorm", "<u2"), ("transmission_roughness_unorm", "<u2"),
+                           ("specular_unorm", "<u2"), ("specular_tint_unorm", "<u2"), ("clearcoat_unorm", "<u2"), ("clearcoat_roughness_unorm", "<u2"),
+                           ("normal_map_strength_unorm", "<u2"), ("_pad", "<u2")])  # rayhip_material
+assert MATERIAL_DTYPE.itemsize == 76
 
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "normals_create", "normals_destroy", "scene_refit_lights", "scene_set_instance_transforms", "scene_set_instance_transforms_device", "scene_set_lights", "scene_set_lights_device", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "normals_create", "normals_destroy", "scene_refit_lights", "scene_set_instance_transforms", "scene_set_instance_transforms_device", "scene_set_lights", "scene_set_lights_device", "scene_set_materials", "scene_set_materials_device", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
@@ -252,6 +258,8 @@ class Library:
             f("scene_set_instance_transforms_device").argtypes = [vp, u32, vp, vp]
             f("scene_set_lights").argtypes = [vp, u32, vp, vp]
             f("scene_set_lights_device").argtypes = [vp, u32, vp, vp]
+            f("scene_set_materials").argtypes = [vp, u32, vp, vp]
+            f("scene_set_materials_device").argtypes = [vp, u32, vp, vp]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -546,12 +554,37 @@ class Context:
         self.L.check(rc)
         return 0
 
+    def set_materials(self, slots, records) -> int:
+        """new records for the material slots `slots` of the uploaded scene: `records` [n] MATERIAL_DTYPE (or [n][19] 32-bit words),
+        complete rayhip_material records whose textures, flags and type are the ones the slot holds.  The triangle lights a named
+        material colours and the light tree follow on the device (rayhip_scene_set_materials; recolouring an emitter needs
+        refit_lights(True)).  Returns as update_vertices(): 0, or 2 where the ABI returns 2; an error raises."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32).ravel()
+        records = np.ascontiguousarray(records)
+        records = (records if records.dtype == np.uint32 else records.view(np.uint32)).reshape(-1, 19)
+        assert len(slots) == len(records)
+        rc = self.L.fn("scene_set_materials")(self._ctx, len(slots), slots.ctypes.data, records.ctypes.data)
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def set_materials_device(self, n: int, slots_pointer: int, records_pointer: int) -> int:
+        """the same from `n` uint32 slots and `n` 76-byte records that are on this context's device already: their addresses as ints (a
+        tensor's data_ptr(), say), 4-byte aligned, the data complete when the call is made (rayhip_scene_set_materials_device)"""
+        rc = self.L.fn("scene_set_materials_device")(self._ctx, int(n), C.c_void_p(int(slots_pointer)), C.c_void_p(int(records_pointer)))
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
     def read_accel(self, which: int) -> np.ndarray:
         """test hook (rayhip_k_read_accel): 0 the BVH2 nodes [n][16] u32 words, 1 the triangle records [n][12] f32, 2 tri_indices [n] u32,
         3 the live top-level leaves [n][7] u32 words (instance slot, lo.xyz, hi.xyz as float bits), by slot, 4 the vertex array as
         VERTEX_DTYPE records, 5 the light tree as LIGHT_NODE_DTYPE records (208 bytes each), 6 its importance rows [nodes][26][4] f32,
         7 the world-space corners of the triangle lights [light slots][4][4] f32, 8 the instance array as MESH_INSTANCE_DTYPE records,
-        9 the light array [light slots][16] u32 words, 10 the leaf summaries of the light refit [light slots][12] f32"""
+        9 the light array [light slots][16] u32 words, 10 the leaf summaries of the light refit [light slots][12] f32, 11 the material
+        array as MATERIAL_DTYPE records"""
         n = C.c_size_t(0)
         self.L.fn("k_read_accel")(self._ctx, which, None, 0, C.byref(n))  # (refused: the size comes back)
         buf = np.zeros(max(int(n.value), 4) // 4, dtype=np.uint32)
@@ -560,7 +593,7 @@ class Context:
         return {0: lambda: buf.reshape(-1, 16), 1: lambda: buf.view(np.float32).reshape(-1, 12), 2: lambda: buf, 3: lambda: buf.reshape(-1, 7),
                 4: lambda: buf.view(VERTEX_DTYPE), 5: lambda: buf.view(LIGHT_NODE_DTYPE), 6: lambda: buf.view(np.float32).reshape(-1, 26, 4),
                 7: lambda: buf.view(np.float32).reshape(-1, 4, 4), 8: lambda: buf.view(MESH_INSTANCE_DTYPE), 9: lambda: buf.reshape(-1, 16),
-                10: lambda: buf.view(np.float32).reshape(-1, 12)}[which]()
+                10: lambda: buf.view(np.float32).reshape(-1, 12), 11: lambda: buf.view(MATERIAL_DTYPE)}[which]()
 
     def render(self, iteration: int, rect=None, cam: Camera = None, flags: int = 0, stats: Stats = None):
         rect = (0, 0, self.w, self.h) if rect is None else rect
