@@ -581,7 +581,7 @@ RAYHIP_API int rayhip_scene_set_instance_transforms_device(rayhip_ctx *ctx, uint
  * light_pose.hip.h).  records[i] is a complete rayhip_light, the layout of rayhip_scene_desc::lights, and replaces light slot slots[i]:
  * colour and the 12 parameter floats may change, word 0 (type, doublesided, cast_shadow, visible, sky_portal, ray_visibility) must be
  * bytewise the word the slot holds, so the counts of visible and blocker lights and the choice of kernels stay.  Sphere, spot,
- * directional, line, rect and disk lights; triangle lights follow their vertices and instances, the environment light needs an upload.
+ * directional, line, rect and disk lights; triangle lights follow their vertices and instances, the environment light its map (rayhip_scene_set_env_map).
  * On the device, before the call returns: the records; the leaf summaries of the named lights (box, axis and angles as the scene build
  * computes them, flux = ((r + g) + b) * area as RebuildLightTree_nolock); the light tree, topology kept, refitted height by height as
  * after a vertex update -- node boxes, quantised child boxes, flux, cone axis and cosines (a directional light's emission cosine is the
@@ -589,8 +589,8 @@ RAYHIP_API int rayhip_scene_set_instance_transforms_device(rayhip_ctx *ctx, uint
  * every later refit, until an upload or an instance update brings the host's tree.  The call needs rayhip_scene_refit_lights on: the
  * switch is what keeps the tree refittable.  It waits for pending passes first; the accumulated image is the caller's to clear.
  * Everything is checked before anything on the device is written -- a refused call has touched nothing.  Returns 0; 1 = a null pointer
- * with n > 0, a slot outside the light array or one li_indices does not name (a freed slot of the pool, a directional light baked into
- * the physical sky), a slot named twice, a held or new record that is a triangle or environment light, a word 0 that differs from the
+ * with n > 0, a slot outside the light array or one li_indices does not name (a freed slot of the pool; a directional light baked into
+ * the physical sky, which rayhip_scene_set_sky moves), a slot named twice, a held or new record that is a triangle or environment light, a word 0 that differs from the
  * held one, a colour or parameter that is not finite; 2 = there is no scene, or rayhip_scene_refit_lights is off or its tables are not
  * prepared.  n == 0 returns 0 and launches nothing.  A later rayhip_scene_update_instances replaces everything by the host's arrays. */
 RAYHIP_API int rayhip_scene_set_lights(rayhip_ctx *ctx, uint32_t n, const uint32_t *slots, const rayhip_light *records);
@@ -623,13 +623,50 @@ RAYHIP_API int rayhip_scene_set_materials(rayhip_ctx *ctx, uint32_t n, const uin
 /* the same from DEVICE memory of the context's device, complete when the call is made and unchanged until it returns; 4-byte aligned. */
 RAYHIP_API int rayhip_scene_set_materials_device(rayhip_ctx *ctx, uint32_t n, const uint32_t *device_slots, const rayhip_material *device_records);
 
+/* THE ENVIRONMENT THAT CHANGES (a sun that moves, a sky whose clouds drift, an HDR map swapped or cross-faded): the last lighting input
+ * that needed a host-side Finalize and an upload (ray_amd/csrc/env_qtree.h, env_qtree.hip.h, rayhip_environment.hip.h).  Three calls:
+ *   rayhip_scene_set_environment   colours and rotations only: no texel changes, no quadtree rebuild (the tree is built without
+ *                                  rotation; env_col does not enter it)
+ *   rayhip_scene_set_env_map       new texels for the environment map the scene holds (RGBE8, row-major, w x h equal to the held
+ *                                  map's level 0), from host memory; _device: from memory of the context's device, 4-byte aligned,
+ *                                  complete when the call is made and unchanged until it returns
+ *   rayhip_scene_set_sky           the physical sky: new records for n of the suns (slots that rayhip_scene_desc::sky_dir_lights names;
+ *                                  word 0 unchanged, floats finite) and / or a new rayhip_sky with its two look-up tables (all three or
+ *                                  none; sizes as held; the caller computes the tables from the atmosphere, as SceneHIP does with the
+ *                                  reference's host functions).  Records and sky are committed and the map is re-baked in place by the
+ *                                  kernel of rayhip_bake_sky; the analytic narrow-ray path reads the same records and sky.
+ * set_env_map and set_sky end alike when the scene has an environment light (env.light_index != 0xffffffff): the map's importance
+ * quadtree is rebuilt on the device as Scene::PrepareEnvMapQTree builds it -- the finest level from 25 taps per cell in the reference's
+ * order, the upper levels as its sums, the same rule for the levels kept; total_lum is the pyramid's own top, not the reference's
+ * running sum, so medium_lum differs from it in the last bits (env_qtree.h) --, the environment light's leaf takes the flux
+ * medium_lum, the light tree and its importance rows are refitted as after rayhip_scene_set_lights, and env.qtree_levels follows.
+ * The pyramid is built beside the live one and swapped in last.  Without an environment light the texels change and nothing else.
+ * Every call waits for pending passes first; the accumulated image is the caller's to clear.  Everything is checked before anything
+ * on the device is written -- a refused call has touched nothing.  Returns 0; 1 = a null pointer, a w / h that is not the held
+ * map's, a slot that is outside the light array, named twice or not one of the sky's suns, a changed word 0, a float that is not
+ * finite, a negative env_col / back_col component, an env_col that would change whether all its components are positive (the condition
+ * under which a scene has its environment light); 2 = the scene needs rayhip_scene_upload: there is none, it has no environment map to
+ * write into (or one too small for a quadtree), it has no physical sky (set_sky), or it has an environment light while
+ * rayhip_scene_refit_lights is off or its tables are not prepared.  Changing the map's size, adding or removing the map or the
+ * environment light need an upload.  A back_map that is another texture than env_map keeps its texels.
+ * A later rayhip_scene_update_instances brings the HOST's environment, quadtree and lights -- everything but the map's texels, which stay
+ * as the device has them: a caller keeps the host scene in step, or makes the call again afterwards.  With several devices, each context
+ * is called. */
+RAYHIP_API int rayhip_scene_set_environment(rayhip_ctx *ctx, const float env_col[3], const float back_col[3], float env_map_rotation, float back_map_rotation);
+RAYHIP_API int rayhip_scene_set_env_map(rayhip_ctx *ctx, int w, int h, const uint32_t *rgbe8);
+RAYHIP_API int rayhip_scene_set_env_map_device(rayhip_ctx *ctx, int w, int h, const uint32_t *device_rgbe8);
+RAYHIP_API int rayhip_scene_set_sky(rayhip_ctx *ctx, uint32_t n, const uint32_t *slots, const rayhip_light *records, const rayhip_sky *sky,
+                                    const float *transmittance_lut, const float *multiscatter_lut);
+
 /* test hook: copy a device array of the acceleration structure to the host. which: 0 BVH2 nodes [0, nodes_used),
  * 1 tris as 48-byte records (un-pitched), 2 tri_indices, 3 the live top-level leaves as (instance slot, lo.xyz, hi.xyz) 7 x 4 bytes each,
  * 4 the vertex array as 44-byte records, 5 the light tree (light_cwnodes, 208 bytes each), 6 its importance rows (light_children,
  * 26 x 16 bytes per node), 7 the world-space corners of the triangle lights (light_tri_geom, 4 x 16 bytes per light slot),
  * 8 the instance array (144 bytes per slot), 9 the light array (64 bytes per slot), 10 the leaf summaries of the light refit (48 bytes
  * per light slot: box lo / hi, flux, cone axis, omega_n, omega_e; needs rayhip_scene_refit_lights), 11 the material array (76 bytes
- * per slot) */
+ * per slot), 12 the environment map's quadtree as rayhip_scene_desc::env_qtree lays it out (the kept levels, finest first), 13 the
+ * 64-byte rayhip_environment the kernels see, followed by total_lum and medium_lum of the last build on the device (0 while the
+ * uploaded quadtree is in use), 14 the environment map's level-0 texels (empty without a map) */
 RAYHIP_API int rayhip_k_read_accel(rayhip_ctx *ctx, int which, void *dst, size_t capacity_bytes, size_t *out_bytes);
 
 /* 1024-entry inverse filter CDF (RendererCPU.h:1234-1258 UpdateFilterTable; upload RendererVK.cpp:386-424) */

@@ -199,6 +199,13 @@ struct rayhip_ctx {
         DevBuf d_flags, d_claim, d_light_emitter;
     } material_checks;
     DevBuf material_stage, material_args, material_counters; // rayhip_scene_set_materials: staged records and slots; the caller's arrays; the counters
+    // the environment changed on the device (rayhip_environment.hip.h; env_qtree.h): the FULL pyramid of the map's res in two halves, used
+    // in turn -- a build never writes the half the scene view points at (after an upload that is `env_qtree` above, and either half is
+    // free) --, and the flags and sums of the last build, on the device and on the host
+    struct EnvBuild {
+        DevBuf pyramid[2], block;
+        float total_lum = 0.0f, medium_lum = 0.0f; // of the pyramid the view points at; 0 while that is the uploaded one
+    } env_build;
     // ---- handles over vertex ranges: skins, morph sets and normal sets.  A record of any kind begins with the same head ...
     struct RangeHead {
         bool live = false;
@@ -1010,7 +1017,7 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
                       &c->skin_palettes, &c->skin_counters, &c->refit.d_slot_flags, &c->refit.d_live, &c->refit.d_slot_claim, &c->instance_stage,
                       &c->instance_args, &c->instance_counters, &c->light_refit.live, &c->light_refit.posed, &c->light_refit.claim, &c->light_stage,
                       &c->light_args, &c->light_counters, &c->material_checks.d_flags, &c->material_checks.d_claim, &c->material_checks.d_light_emitter,
-                      &c->material_stage, &c->material_args, &c->material_counters}) {
+                      &c->material_stage, &c->material_args, &c->material_counters, &c->env_build.pyramid[0], &c->env_build.pyramid[1], &c->env_build.block}) {
         b->release();
     }
     for (hipEvent_t e : c->events) {

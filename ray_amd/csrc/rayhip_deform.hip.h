@@ -172,8 +172,8 @@ static int upload_material_checks(rayhip_ctx *c, const rayhip_scene_desc *d, con
 
 // ---- what a light refit needs of the lights that are on the device (rayhip_scene_refit_lights; light_refit.h) ------------------------
 // the tree's nodes sorted by height, the leaf summary table (lights that are no triangles complete: they do not move with vertices;
-// their flux from the tree as uploaded, since the environment light's needs the quadtree's mean luminance, which never reaches the
-// device), the flux scales of the inner slots (light_refit.h: slot_scales, one host refit at the pose the tree was built at) and the
+// their flux from the tree as uploaded, since the environment light's is the quadtree's mean luminance, which the device computes
+// only when the map changes there: rayhip_environment.hip.h), the flux scales of the inner slots (light_refit.h: slot_scales, one host refit at the pose the tree was built at) and the
 // scratch of the level launches.  `d`: the light arrays, vertices, indices and instances as they are on the device.
 static int prepare_light_refit(rayhip_ctx *c, const rayhip_scene_desc *d) {
     const rayhip_light *lights = d->lights;

@@ -513,7 +513,9 @@ static int upload_bottom_level(rayhip_ctx *c, const rayhip_scene_desc *d, rayhip
 
 // the arrays the shade stage reads: materials per triangle and their table, vertices and indices, and the vertices gathered per
 // triangle on the device from the arrays just uploaded (shade_point.h: fill_tri_verts)
-static int upload_shading_arrays(rayhip_ctx *c, const rayhip_scene_desc *d, const bool all_sides_solid, const UploadTrace &trace) {
+// `materials_used`: one byte per material slot, 1 where a reachable triangle or a Mix operand uses it (scene_validate.h)
+static int upload_shading_arrays(rayhip_ctx *c, const rayhip_scene_desc *d, const bool all_sides_solid, const std::vector<uint8_t> &materials_used,
+                                 const UploadTrace &trace) {
     UP(tri_materials)
     // is there a triangle side that is not plainly solid?  (the closest-hit kernels skip the per-hit material fetch when not; round 4: judged
     // over the reachable triangles -- the headline scene's pool has unused slots, and the flag had never been set for it)
@@ -521,10 +523,12 @@ static int upload_shading_arrays(rayhip_ctx *c, const rayhip_scene_desc *d, cons
     trace(all_sides_solid ? "every reachable triangle side is solid" : "some triangle sides are not solid");
     UP(materials)
     { // can any surface change a ray's stack of refractive indices?  (ShadeParams::plain_ior: if not, the passes leave the rays' ior plane alone)
+        // Judged over the slots in use, like all_solid above: an unused slot of the host's pool holds whatever the heap held
         bool refracts = false;
         for (uint32_t i = 0; i < d->materials_count; ++i) {
             const rayhip_material &m = d->materials[i];
-            refracts |= m.type == NODE_REFRACTIVE || (m.type == NODE_PRINCIPLED && m.transmission_unorm != 0);
+            refracts |= (i >= materials_used.size() || materials_used[i] != 0) &&
+                        (m.type == NODE_REFRACTIVE || (m.type == NODE_PRINCIPLED && m.transmission_unorm != 0));
         }
         c->plain_ior = !refracts && !getenv("RAYHIP_NO_PLAIN_IOR");
         trace(refracts ? "refractive surfaces: rays carry their ior stacks" : "no refractive surface: the ior plane of the rays is not used");
@@ -604,7 +608,7 @@ int rayhip_scene_upload(rayhip_ctx *c, const rayhip_scene_desc *d_in) {
         return 1;
     }
     trace("bvh uploaded");
-    if (upload_shading_arrays(c, d, all_sides_solid, trace)) {
+    if (upload_shading_arrays(c, d, all_sides_solid, materials_used, trace)) {
         return 1;
     }
     trace("tri_verts done");
@@ -895,6 +899,31 @@ int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_byt
         src = c->light_refit.leaf.p, bytes = size_t(c->light_refit.lights_count) * sizeof(rayhip_light_refit::Summary);
     } else if (which == 11) {
         src = c->materials.p, bytes = size_t(c->geometry.materials) * sizeof(rayhip_material);
+    } else if (which == 12) { // the quadtree the kernels walk: the kept levels, finest first, wherever they lie (uploaded, or built on the device)
+        size_t quads = 0;
+        for (int lod = 0; lod < c->sc.env.qtree_levels; ++lod) {
+            quads += size_t(1) << (2 * (c->sc.env.qtree_levels - 1 - lod));
+        }
+        src = c->sc.env_qtree + c->sc.env_qtree_offset[0], bytes = quads * sizeof(float4);
+    } else if (which == 13) { // (host memory: the view's environment and the sums of the last build on the device)
+        uint8_t out[sizeof(rayhip_environment) + 8];
+        memcpy(out, &c->sc.env, sizeof(rayhip_environment));
+        const bool built = c->sc.env_qtree != c->env_qtree.as<float4>();
+        const float sums[2] = {built ? c->env_build.total_lum : 0.0f, built ? c->env_build.medium_lum : 0.0f};
+        memcpy(out + sizeof(rayhip_environment), sums, 8);
+        *out_bytes = sizeof(out);
+        if (sizeof(out) > capacity_bytes) {
+            return fail("rayhip_k_read_accel: %zu bytes do not fit %zu", sizeof(out), capacity_bytes);
+        }
+        memcpy(dst, out, sizeof(out));
+        return 0;
+    } else if (which == 14) {
+        HeldEnvMap m;
+        const int rc = held_env_map(c, "rayhip_k_read_accel", m); // (2: the scene has no map, and the array is empty)
+        if (rc == 1) {
+            return 1;
+        }
+        src = m.texels, bytes = rc ? 0 : size_t(m.w) * size_t(m.h) * sizeof(uint32_t);
     } else {
         return fail("rayhip_k_read_accel: no array %d", which);
     }

@@ -126,7 +126,7 @@ assert MATERIAL_DTYPE.itemsize == 76
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "normals_create", "normals_destroy", "scene_refit_lights", "scene_set_instance_transforms", "scene_set_instance_transforms_device", "scene_set_lights", "scene_set_lights_device", "scene_set_materials", "scene_set_materials_device", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "normals_create", "normals_destroy", "scene_refit_lights", "scene_set_instance_transforms", "scene_set_instance_transforms_device", "scene_set_lights", "scene_set_lights_device", "scene_set_materials", "scene_set_materials_device", "scene_set_environment", "scene_set_env_map", "scene_set_env_map_device", "scene_set_sky", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
@@ -260,6 +260,10 @@ class Library:
             f("scene_set_lights_device").argtypes = [vp, u32, vp, vp]
             f("scene_set_materials").argtypes = [vp, u32, vp, vp]
             f("scene_set_materials_device").argtypes = [vp, u32, vp, vp]
+            f("scene_set_environment").argtypes = [vp, vp, vp, C.c_float, C.c_float]
+            f("scene_set_env_map").argtypes = [vp, C.c_int, C.c_int, vp]
+            f("scene_set_env_map_device").argtypes = [vp, C.c_int, C.c_int, vp]
+            f("scene_set_sky").argtypes = [vp, u32, vp, vp, vp, vp, vp]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -578,13 +582,63 @@ class Context:
         self.L.check(rc)
         return 0
 
+    def _changed(self, rc: int) -> int:
+        if rc == 2:
+            return 2
+        self.L.check(rc)
+        return 0
+
+    def set_environment(self, env_col, back_col, env_map_rotation: float, back_map_rotation: float) -> int:
+        """new colours and rotations of the environment; no texel changes, no quadtree (rayhip_scene_set_environment).  Returns as
+        update_vertices(): 0, or 2 where the ABI returns 2; an error raises."""
+        e, b = np.ascontiguousarray(env_col, dtype=np.float32), np.ascontiguousarray(back_col, dtype=np.float32)
+        assert e.size == 3 and b.size == 3
+        return self._changed(self.L.fn("scene_set_environment")(self._ctx, e.ctypes.data, b.ctypes.data, float(env_map_rotation), float(back_map_rotation)))
+
+    def set_env_map(self, rgbe8) -> int:
+        """new texels for the environment map the scene holds: `rgbe8` [h][w] uint32 (or [h][w][4] uint8) RGBE8 of the held map's size.
+        Quadtree, the environment light's flux and the light tree follow on the device (rayhip_scene_set_env_map; a scene with an
+        environment light needs refit_lights(True)).  Returns as set_environment()."""
+        t = np.ascontiguousarray(rgbe8)
+        t = t.view(np.uint32).reshape(t.shape[0], t.shape[1]) if t.dtype == np.uint8 else np.ascontiguousarray(t, dtype=np.uint32)
+        assert t.ndim == 2
+        return self._changed(self.L.fn("scene_set_env_map")(self._ctx, t.shape[1], t.shape[0], t.ctypes.data))
+
+    def set_env_map_device(self, w: int, h: int, texels_pointer: int) -> int:
+        """the same from w x h uint32 that are on this context's device already: their address as an int (a tensor's data_ptr(), say),
+        4-byte aligned, the data complete when the call is made (rayhip_scene_set_env_map_device)"""
+        return self._changed(self.L.fn("scene_set_env_map_device")(self._ctx, int(w), int(h), C.c_void_p(int(texels_pointer))))
+
+    def set_sky(self, slots=(), records=None, sky=None, transmittance_lut=None, multiscatter_lut=None) -> int:
+        """the physical sky: new records [n][16] 32-bit words for the suns in light slots `slots`, and / or a new 256-byte rayhip_sky
+        (bytes or an array) with its two look-up tables (float32; all three or none).  The map is re-baked in place, then as
+        set_env_map() (rayhip_scene_set_sky)."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32).ravel()
+        rec = np.zeros((0, 16), np.uint32) if records is None else np.ascontiguousarray(records)
+        rec = (rec if rec.dtype == np.uint32 else rec.view(np.uint32)).reshape(-1, 16)
+        assert len(slots) == len(rec)
+        keep = []
+
+        def ptr(a, dtype):
+            if a is None:
+                return None
+            a = np.frombuffer(a, dtype=dtype).copy() if isinstance(a, (bytes, bytearray)) else np.ascontiguousarray(a).view(dtype).ravel()
+            keep.append(a)
+            return a.ctypes.data
+
+        s = ptr(sky, np.uint8)
+        assert s is None or keep[-1].nbytes == 256
+        return self._changed(self.L.fn("scene_set_sky")(self._ctx, len(slots), slots.ctypes.data if len(slots) else None, rec.ctypes.data if len(slots) else None,
+                                                        s, ptr(transmittance_lut, np.float32), ptr(multiscatter_lut, np.float32)))
+
     def read_accel(self, which: int) -> np.ndarray:
         """test hook (rayhip_k_read_accel): 0 the BVH2 nodes [n][16] u32 words, 1 the triangle records [n][12] f32, 2 tri_indices [n] u32,
         3 the live top-level leaves [n][7] u32 words (instance slot, lo.xyz, hi.xyz as float bits), by slot, 4 the vertex array as
         VERTEX_DTYPE records, 5 the light tree as LIGHT_NODE_DTYPE records (208 bytes each), 6 its importance rows [nodes][26][4] f32,
         7 the world-space corners of the triangle lights [light slots][4][4] f32, 8 the instance array as MESH_INSTANCE_DTYPE records,
         9 the light array [light slots][16] u32 words, 10 the leaf summaries of the light refit [light slots][12] f32, 11 the material
-        array as MATERIAL_DTYPE records"""
+        array as MATERIAL_DTYPE records, 12 the environment map's quadtree [quads][4] f32 (the kept levels, finest first), 13 the 64-byte
+        rayhip_environment the kernels see + total_lum, medium_lum as 18 u32 words, 14 the environment map's level-0 texels [w * h] u32"""
         n = C.c_size_t(0)
         self.L.fn("k_read_accel")(self._ctx, which, None, 0, C.byref(n))  # (refused: the size comes back)
         buf = np.zeros(max(int(n.value), 4) // 4, dtype=np.uint32)
@@ -593,7 +647,8 @@ class Context:
         return {0: lambda: buf.reshape(-1, 16), 1: lambda: buf.view(np.float32).reshape(-1, 12), 2: lambda: buf, 3: lambda: buf.reshape(-1, 7),
                 4: lambda: buf.view(VERTEX_DTYPE), 5: lambda: buf.view(LIGHT_NODE_DTYPE), 6: lambda: buf.view(np.float32).reshape(-1, 26, 4),
                 7: lambda: buf.view(np.float32).reshape(-1, 4, 4), 8: lambda: buf.view(MESH_INSTANCE_DTYPE), 9: lambda: buf.reshape(-1, 16),
-                10: lambda: buf.view(np.float32).reshape(-1, 12), 11: lambda: buf.view(MATERIAL_DTYPE)}[which]()
+                10: lambda: buf.view(np.float32).reshape(-1, 12), 11: lambda: buf.view(MATERIAL_DTYPE),
+                12: lambda: buf.view(np.float32).reshape(-1, 4), 13: lambda: buf, 14: lambda: buf}[which]()
 
     def render(self, iteration: int, rect=None, cam: Camera = None, flags: int = 0, stats: Stats = None):
         rect = (0, 0, self.w, self.h) if rect is None else rect
