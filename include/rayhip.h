@@ -658,6 +658,40 @@ RAYHIP_API int rayhip_scene_set_env_map_device(rayhip_ctx *ctx, int w, int h, co
 RAYHIP_API int rayhip_scene_set_sky(rayhip_ctx *ctx, uint32_t n, const uint32_t *slots, const rayhip_light *records, const rayhip_sky *sky,
                                     const float *transmittance_lut, const float *multiscatter_lut);
 
+/* TEXTURES THAT CHANGE (a base-colour map that animates, a flip-book, a video frame, a normal or roughness map written by the caller's
+ * own kernel): new texels for ONE texture the uploaded scene holds, and nothing else -- no host AddTexture, no export, no upload
+ * (ray_amd/csrc/texture_update.h, texture_update.hip.h, rayhip_textures.hip.h).  `handle` is the reference's texture handle word as
+ * materials hold it (storage << 28 | flags << 24 | index): storage and index name the texture, the YCoCg bit says how a storage-5
+ * texture is encoded.  The handle's flags and the handles inside materials never change: a caller who gives a normal map a blue
+ * channel that would have flipped reconstruct_z at AddTexture time keeps the flag the scene was built with.
+ *   rayhip_scene_set_texture          w x h RGBA8 words (one uint32_t per texel, row-major; R in the low byte) from host memory; w x h must
+ *                                     be level 0 of the held texture.  Texels arrive in the orientation the scene stores them: no DX flip,
+ *                                     and a normal map's green as stored.  _device: from memory of the context's device, 4-byte aligned,
+ *                                     complete when the call is made and unchanged until it returns.
+ *     storages 0-3 (RGBA, RGB, RG, R; one level -- the reference's swizzled storage builds no mips): the words are copied over level 0
+ *                                     as they are, so the caller supplies the channel replication an upload produces: RGB a = b;
+ *                                     RG b = a = g; R all four bytes equal.
+ *     storages 5 with the YCoCg bit, 6, 7 (BC3 over YCoCg from R, G, B; BC4 from R; BC5 from R and G) on a scene uploaded with
+ *                                     RAYHIP_TEX_RAW_BC: every level the texture holds (offset[lod] != offset[lod - 1]) is rebuilt in
+ *                                     place on the device -- the reference's real-time block compressor and its mip builder (each level
+ *                                     the integer average of the SOURCE channels of the one above), restated bit for bit.
+ *   rayhip_scene_set_texture_blocks   ready 4 x 4 blocks for the whole mip chain of a texture of any block storage 4-7, from host memory:
+ *                                     level 0 first, each level in row-major tile order; `bytes` must equal what the texture holds.  The
+ *                                     only route for BC1 and for BC3 without the YCoCg bit: the reference itself never compresses into
+ *                                     those two and accepts them only pre-compressed, so there is nothing to hold a device compressor
+ *                                     against.
+ * Every call waits for pending passes first and returns when the device work is done; the accumulated image is the caller's to clear.
+ * Every check is made on the host before anything is written -- a refused call has touched nothing.  Returns 0; 1 = a null pointer,
+ * a handle whose storage or index is outside tex_table / textures, a w / h or `bytes` that is not the held texture's, a device pointer
+ * that is not 4-byte aligned, a texel storage given to _blocks, the texture that is the scene's env.env_map (rayhip_scene_set_env_map
+ * changes that one and rebuilds its quadtree); 2 = the scene needs rayhip_scene_upload: there is none, storage 4 or 5 without the YCoCg
+ * bit was given to the texel forms, or a block storage on a scene uploaded without RAYHIP_TEX_RAW_BC.  Changing a texture's size, mip
+ * count or storage, adding or removing textures need an upload.  A later rayhip_scene_update_instances does not touch texels.  With
+ * several devices, each context is called. */
+RAYHIP_API int rayhip_scene_set_texture(rayhip_ctx *ctx, uint32_t handle, int w, int h, const uint32_t *rgba8);
+RAYHIP_API int rayhip_scene_set_texture_device(rayhip_ctx *ctx, uint32_t handle, int w, int h, const uint32_t *device_rgba8);
+RAYHIP_API int rayhip_scene_set_texture_blocks(rayhip_ctx *ctx, uint32_t handle, const void *blocks, size_t bytes);
+
 /* test hook: copy a device array of the acceleration structure to the host. which: 0 BVH2 nodes [0, nodes_used),
  * 1 tris as 48-byte records (un-pitched), 2 tri_indices, 3 the live top-level leaves as (instance slot, lo.xyz, hi.xyz) 7 x 4 bytes each,
  * 4 the vertex array as 44-byte records, 5 the light tree (light_cwnodes, 208 bytes each), 6 its importance rows (light_children,
@@ -666,7 +700,8 @@ RAYHIP_API int rayhip_scene_set_sky(rayhip_ctx *ctx, uint32_t n, const uint32_t 
  * per light slot: box lo / hi, flux, cone axis, omega_n, omega_e; needs rayhip_scene_refit_lights), 11 the material array (76 bytes
  * per slot), 12 the environment map's quadtree as rayhip_scene_desc::env_qtree lays it out (the kept levels, finest first), 13 the
  * 64-byte rayhip_environment the kernels see, followed by total_lum and medium_lum of the last build on the device (0 while the
- * uploaded quadtree is in use), 14 the environment map's level-0 texels (empty without a map) */
+ * uploaded quadtree is in use), 14 the environment map's level-0 texels (empty without a map), 15 the whole texel pool, 16 the
+ * rayhip_texture records followed by tex_table[8] and texture_flags */
 RAYHIP_API int rayhip_k_read_accel(rayhip_ctx *ctx, int which, void *dst, size_t capacity_bytes, size_t *out_bytes);
 
 /* 1024-entry inverse filter CDF (RendererCPU.h:1234-1258 UpdateFilterTable; upload RendererVK.cpp:386-424) */

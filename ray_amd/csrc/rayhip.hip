@@ -38,6 +38,7 @@
 #include "light_pose.hip.h"
 #include "materials.hip.h"
 #include "env_qtree.hip.h"
+#include "texture_update.hip.h"
 #include "instances.hip.h"
 #include "scene_blob.h"
 #include "scene_rebuild.h"
@@ -53,6 +54,7 @@ using namespace rt;
 #include "rayhip_trace.hip.h"
 #include "rayhip_deform.hip.h"
 #include "rayhip_environment.hip.h"
+#include "rayhip_textures.hip.h"
 #include "rayhip_upload.hip.h"
 #include "rayhip_render.hip.h"
 #include "rayhip_denoise.hip.h"

@@ -144,6 +144,7 @@ struct rayhip_ctx {
     uint32_t tlas_half = 0; // which half of the reserved node slots the next rebuilt top level goes to (the live one sits in the other)
     int wide = 0; // the wide BLAS form the kernels walk: 4 (rt_bvh4.h, default), 8 (rt_bvh8.h) or 0 (the reference's BVH2)
     uint32_t tex_table[8] = {}, textures_count = 0, tex_flags = 0;
+    uint32_t texels_count = 0; // words of the texel pool as uploaded (`texels` only grows)
     struct { uint32_t vertices, vtx_indices, tri_materials, materials; } geometry = {};
     uint32_t instances_count = 0; // mesh instances on the device (scene_upload and scene_update set it)
     // ---- deforming the scene that is on the device (rayhip_deform.hip.h): the tables an upload or instance update leaves for a vertex
@@ -206,6 +207,8 @@ struct rayhip_ctx {
         DevBuf pyramid[2], block;
         float total_lum = 0.0f, medium_lum = 0.0f; // of the pyramid the view points at; 0 while that is the uploaded one
     } env_build;
+    // rayhip_scene_set_texture: the averaged texels of the mip being compressed, the source of the next one; two halves used in turn (grow-only)
+    DevBuf texture_stage;
     // ---- handles over vertex ranges: skins, morph sets and normal sets.  A record of any kind begins with the same head ...
     struct RangeHead {
         bool live = false;
@@ -1017,7 +1020,7 @@ void rayhip_ctx_destroy(rayhip_ctx *c) {
                       &c->skin_palettes, &c->skin_counters, &c->refit.d_slot_flags, &c->refit.d_live, &c->refit.d_slot_claim, &c->instance_stage,
                       &c->instance_args, &c->instance_counters, &c->light_refit.live, &c->light_refit.posed, &c->light_refit.claim, &c->light_stage,
                       &c->light_args, &c->light_counters, &c->material_checks.d_flags, &c->material_checks.d_claim, &c->material_checks.d_light_emitter,
-                      &c->material_stage, &c->material_args, &c->material_counters, &c->env_build.pyramid[0], &c->env_build.pyramid[1], &c->env_build.block}) {
+                      &c->material_stage, &c->material_args, &c->material_counters, &c->env_build.pyramid[0], &c->env_build.pyramid[1], &c->env_build.block, &c->texture_stage}) {
         b->release();
     }
     for (hipEvent_t e : c->events) {

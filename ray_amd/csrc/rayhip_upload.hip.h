@@ -558,6 +558,7 @@ static int upload_textures_and_env(rayhip_ctx *c, const rayhip_scene_desc *d) {
     HIP_TRY(hipStreamSynchronize(c->stream)); // host arrays may go away after this call
     memcpy(c->tex_table, d->tex_table, sizeof(c->tex_table));
     c->textures_count = d->textures_count;
+    c->texels_count = d->texels_count;
     c->tex_flags = d->texture_flags;
     return 0;
 }
@@ -924,6 +925,20 @@ int rayhip_k_read_accel(rayhip_ctx *c, int which, void *dst, size_t capacity_byt
             return 1;
         }
         src = m.texels, bytes = rc ? 0 : size_t(m.w) * size_t(m.h) * sizeof(uint32_t);
+    } else if (which == 15) {
+        src = c->texels.p, bytes = size_t(c->texels_count) * sizeof(uint32_t);
+    } else if (which == 16) { // (the records from the device; the table and the flags are the host's)
+        const size_t records = size_t(c->textures_count) * sizeof(rayhip_texture);
+        *out_bytes = records + sizeof(c->tex_table) + sizeof(uint32_t);
+        if (*out_bytes > capacity_bytes) {
+            return fail("rayhip_k_read_accel: %zu bytes do not fit %zu", *out_bytes, capacity_bytes);
+        }
+        if (records) {
+            HIP_TRY(hipMemcpy(dst, c->textures.p, records, hipMemcpyDeviceToHost));
+        }
+        memcpy(static_cast<uint8_t *>(dst) + records, c->tex_table, sizeof(c->tex_table));
+        memcpy(static_cast<uint8_t *>(dst) + records + sizeof(c->tex_table), &c->tex_flags, sizeof(uint32_t));
+        return 0;
     } else {
         return fail("rayhip_k_read_accel: no array %d", which);
     }

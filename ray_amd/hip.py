@@ -126,7 +126,7 @@ assert MATERIAL_DTYPE.itemsize == 76
 # every symbol include/rayhip.h declares (tests check that the built library exports all of them)
 ENTRY_POINTS = (
     "last_error", "abi_version", "device_count", "ctx_create", "ctx_destroy", "ctx_device_name", "upload_static", "resize", "clear",
-    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "normals_create", "normals_destroy", "scene_refit_lights", "scene_set_instance_transforms", "scene_set_instance_transforms_device", "scene_set_lights", "scene_set_lights_device", "scene_set_materials", "scene_set_materials_device", "scene_set_environment", "scene_set_env_map", "scene_set_env_map_device", "scene_set_sky", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
+    "scene_upload", "bake_sky", "bake_sky_blob", "scene_bvh_width", "closest_hit_form", "direct_entry", "scene_upload_blob", "scene_update_instances", "scene_update_instances_blob", "scene_update_vertices", "scene_update_vertices_blob", "scene_update_vertices_device", "skin_create", "skin_destroy", "scene_pose_skins", "morph_create", "morph_destroy", "scene_pose", "normals_create", "normals_destroy", "scene_refit_lights", "scene_set_instance_transforms", "scene_set_instance_transforms_device", "scene_set_lights", "scene_set_lights_device", "scene_set_materials", "scene_set_materials_device", "scene_set_environment", "scene_set_env_map", "scene_set_env_map_device", "scene_set_sky", "scene_set_texture", "scene_set_texture_device", "scene_set_texture_blocks", "set_filter_table", "render", "render_batch", "max_batch", "reserve_batch", "set_tonemap_lut", "denoise_nlm", "readback", "readback_device", "set_raw_device",
     "sync", "set_shard", "get_trav_counters", "get_trav_timing", "get_stage_times", "k_generate_primary_rays", "k_intersect_closest",
     "k_intersect_shadow", "k_scrambled_rand", "k_shade",
     "comm_create", "comm_probe", "comm_info", "comm_unique_id", "comm_create_rank", "comm_bind", "comm_reduce_framebuffers", "comm_destroy",
@@ -264,6 +264,9 @@ class Library:
             f("scene_set_env_map").argtypes = [vp, C.c_int, C.c_int, vp]
             f("scene_set_env_map_device").argtypes = [vp, C.c_int, C.c_int, vp]
             f("scene_set_sky").argtypes = [vp, u32, vp, vp, vp, vp, vp]
+            f("scene_set_texture").argtypes = [vp, u32, C.c_int, C.c_int, vp]
+            f("scene_set_texture_device").argtypes = [vp, u32, C.c_int, C.c_int, vp]
+            f("scene_set_texture_blocks").argtypes = [vp, u32, vp, C.c_size_t]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -631,6 +634,26 @@ class Context:
         return self._changed(self.L.fn("scene_set_sky")(self._ctx, len(slots), slots.ctypes.data if len(slots) else None, rec.ctypes.data if len(slots) else None,
                                                         s, ptr(transmittance_lut, np.float32), ptr(multiscatter_lut, np.float32)))
 
+    def set_texture(self, handle: int, rgba8) -> int:
+        """new texels for the texture `handle` names (the reference's handle word): `rgba8` [h][w] uint32 (or [h][w][4] uint8) of the
+        size of the held texture's level 0.  An uncompressed storage takes the words as they are; the BC3 (YCoCg), BC4 and BC5 storages
+        are compressed and their mips rebuilt on the device (rayhip_scene_set_texture).  Returns as set_environment()."""
+        t = np.ascontiguousarray(rgba8)
+        t = t.view(np.uint32).reshape(t.shape[0], t.shape[1]) if t.dtype == np.uint8 else np.ascontiguousarray(t, dtype=np.uint32)
+        assert t.ndim == 2
+        return self._changed(self.L.fn("scene_set_texture")(self._ctx, int(handle), t.shape[1], t.shape[0], t.ctypes.data))
+
+    def set_texture_device(self, handle: int, w: int, h: int, texels_pointer: int) -> int:
+        """the same from w x h uint32 that are on this context's device already: their address as an int (a tensor's data_ptr(), say),
+        4-byte aligned, the data complete when the call is made (rayhip_scene_set_texture_device)"""
+        return self._changed(self.L.fn("scene_set_texture_device")(self._ctx, int(handle), int(w), int(h), C.c_void_p(int(texels_pointer))))
+
+    def set_texture_blocks(self, handle: int, blocks) -> int:
+        """ready 4 x 4 blocks (bytes, or a uint8 array) for the whole mip chain of a texture of a block storage, level 0 first
+        (rayhip_scene_set_texture_blocks)"""
+        b = np.frombuffer(blocks, dtype=np.uint8).copy() if isinstance(blocks, (bytes, bytearray)) else np.ascontiguousarray(blocks).view(np.uint8).ravel()
+        return self._changed(self.L.fn("scene_set_texture_blocks")(self._ctx, int(handle), b.ctypes.data, b.nbytes))
+
     def read_accel(self, which: int) -> np.ndarray:
         """test hook (rayhip_k_read_accel): 0 the BVH2 nodes [n][16] u32 words, 1 the triangle records [n][12] f32, 2 tri_indices [n] u32,
         3 the live top-level leaves [n][7] u32 words (instance slot, lo.xyz, hi.xyz as float bits), by slot, 4 the vertex array as
@@ -638,7 +661,8 @@ class Context:
         7 the world-space corners of the triangle lights [light slots][4][4] f32, 8 the instance array as MESH_INSTANCE_DTYPE records,
         9 the light array [light slots][16] u32 words, 10 the leaf summaries of the light refit [light slots][12] f32, 11 the material
         array as MATERIAL_DTYPE records, 12 the environment map's quadtree [quads][4] f32 (the kept levels, finest first), 13 the 64-byte
-        rayhip_environment the kernels see + total_lum, medium_lum as 18 u32 words, 14 the environment map's level-0 texels [w * h] u32"""
+        rayhip_environment the kernels see + total_lum, medium_lum as 18 u32 words, 14 the environment map's level-0 texels [w * h] u32,
+        15 the whole texel pool as u32 words, 16 the rayhip_texture records (36 words each), tex_table[8] and texture_flags as u32 words"""
         n = C.c_size_t(0)
         self.L.fn("k_read_accel")(self._ctx, which, None, 0, C.byref(n))  # (refused: the size comes back)
         buf = np.zeros(max(int(n.value), 4) // 4, dtype=np.uint32)
@@ -648,7 +672,7 @@ class Context:
                 4: lambda: buf.view(VERTEX_DTYPE), 5: lambda: buf.view(LIGHT_NODE_DTYPE), 6: lambda: buf.view(np.float32).reshape(-1, 26, 4),
                 7: lambda: buf.view(np.float32).reshape(-1, 4, 4), 8: lambda: buf.view(MESH_INSTANCE_DTYPE), 9: lambda: buf.reshape(-1, 16),
                 10: lambda: buf.view(np.float32).reshape(-1, 12), 11: lambda: buf.view(MATERIAL_DTYPE),
-                12: lambda: buf.view(np.float32).reshape(-1, 4), 13: lambda: buf, 14: lambda: buf}[which]()
+                12: lambda: buf.view(np.float32).reshape(-1, 4), 13: lambda: buf, 14: lambda: buf, 15: lambda: buf, 16: lambda: buf}[which]()
 
     def render(self, iteration: int, rect=None, cam: Camera = None, flags: int = 0, stats: Stats = None):
         rect = (0, 0, self.w, self.h) if rect is None else rect
