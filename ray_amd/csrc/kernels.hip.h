@@ -353,6 +353,50 @@ __global__ void __launch_bounds__(WAVE, MINW) k_trace_closest(const SceneView sc
 #endif
 }
 
+// ---- what the persistent kernels below share (K2 refill, K2 pooled, K3 refill) and k_trace_shadow with them -------------------------------
+// the parameters of the layer a (virtual) pixel belongs to: a later iteration of a batched pass has its own sample index and seed (the
+// twin of layer_params(ShadeParams), shade_kernels.hip)
+__device__ __forceinline__ TraceParams layer_params(const TraceParams &tp, const uint32_t layer) {
+    TraceParams p = tp;
+    if (layer != 0) {
+        p.iteration = tp.iteration + int(layer);
+        p.rand_seed = layer_rand_seed(p.iteration);
+    }
+    return p;
+}
+
+// end of Traverse_TLAS_WithStack_*: the primitive index indirection (a negative index is a hit on the back face and stays one)
+__device__ __forceinline__ int resolve_prim_index(const SceneView &sc, const int prim_index) {
+    return prim_index < 0 ? -int(sc.tri_indices[-prim_index - 1]) - 1 : int(sc.tri_indices[prim_index]);
+}
+
+// One step of a lane's top-level walk at a node of the reference's BVH2: near child first, far child saved, or pop.  The lane state is
+// that of the flat kernels -- the topmost entry in a register (`tos`), the rest at st[0 .. size) through write_at / read_at -- and NOT
+// the push / pop stack of bvh2_node_step (rt_traverse.h), which the nested walks keep: the two are apart on purpose.
+template <class Stack>
+__device__ __forceinline__ void top_level_node_step(const rayhip_bvh2_node *nodes, const f3 ro, const f3 inv, const float t, Stack &st,
+                                                    uint32_t &cur, uint32_t &tos, uint32_t &size) {
+    const float4 *np = reinterpret_cast<const float4 *>(nodes + cur);
+    const float4 d0 = np[0], d1 = np[1], d2 = np[2], links = np[3];
+    const uint32_t left_child = float_as_uint(links.x), right_child = float_as_uint(links.y);
+    const float ch0_min[3] = {d0.x, d0.z, d2.x}, ch0_max[3] = {d0.y, d0.w, d2.y};
+    const float ch1_min[3] = {d1.x, d1.z, d2.z}, ch1_max[3] = {d1.y, d1.w, d2.w};
+    float ch0_dist, ch1_dist;
+    const bool ch0_res = bbox_test(ro, inv, t, ch0_min, ch0_max, ch0_dist);
+    const bool ch1_res = bbox_test(ro, inv, t, ch1_min, ch1_max, ch1_dist);
+    if (!ch0_res && !ch1_res) {
+        cur = tos;
+        tos = st.read_at(--size);
+    } else if (ch0_res && ch1_res) {
+        const bool swap = ch1_dist < ch0_dist;
+        st.write_at(size++, tos);
+        tos = swap ? left_child : right_child;
+        cur = swap ? right_child : left_child;
+    } else {
+        cur = ch0_res ? left_child : right_child;
+    }
+}
+
 #include "kernels_closest_refill.hip.h"
 #include "kernels_closest_pool.hip.h"
 #include "kernels_shadow.hip.h"

@@ -236,12 +236,7 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
         {
             const bool in_fin = (lvl == TLAS) && (cur == BVH4_SENTINEL);
             if (in_fin) {
-                // end of Traverse_TLAS_WithStack_ClosestHit: primitive index indirection (runs on misses too)
-                if (h.prim_index < 0) {
-                    h.prim_index = -int(sc.tri_indices[-h.prim_index - 1]) - 1;
-                } else {
-                    h.prim_index = int(sc.tri_indices[h.prim_index]);
-                }
+                h.prim_index = resolve_prim_index(sc, h.prim_index); // (runs on misses too)
                 bool again = false;
                 if (res && !hit_side_is_solid(sc, h)) { // tail of the IntersectScene round (rare: the hit is not on a solid surface): what does it mean
                     const float4 cc = rays.c_cs[slot];
@@ -251,11 +246,7 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
                     r.cone_spread = cc.w;
                     r.xy = xd.x, r.depth = xd.y;
                     const uint32_t xy_virtual = r.xy, layer = xy_layer(xy_virtual, layers);
-                    TraceParams tpl = tp;
-                    if (layer != 0) { // a later iteration of the batch: its own sample index / seed, keyed by the real pixel
-                        tpl.iteration = tp.iteration + int(layer);
-                        tpl.rand_seed = layer_rand_seed(tpl.iteration);
-                    }
+                    const TraceParams tpl = layer_params(tp, layer);
                     r.xy = xy_real(xy_virtual, layers, layer); // (interleaved layers: layer 0 is not the real pixel either)
                     const uint32_t rand_hash = hash_combine(hash(r.xy), tpl.rand_seed);
                     uint32_t rand_dim = RAND_DIM_BASE_COUNT + get_total_depth(r.depth) * RAND_DIM_BOUNCE_COUNT;
@@ -335,26 +326,8 @@ __global__ void __launch_bounds__(WAVE, RT_REFILL_MIN_WAVES) k_trace_closest_ref
             st_tlas += 1;
 #endif
             if (in_c) {
-                if ((cur & BVH2_PRIM_COUNT_BITS) == 0) { // TLAS node (reference BVH2): near child first, far child pushed
-                    const f3 inv = safe_invert(rd);
-                    const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + cur);
-                    const float4 d0 = np[0], d1 = np[1], d2 = np[2], links = np[3];
-                    const uint32_t left_child = float_as_uint(links.x), right_child = float_as_uint(links.y);
-                    const float ch0_min[3] = {d0.x, d0.z, d2.x}, ch0_max[3] = {d0.y, d0.w, d2.y};
-                    const float ch1_min[3] = {d1.x, d1.z, d2.z}, ch1_max[3] = {d1.y, d1.w, d2.w};
-                    float ch0_dist, ch1_dist;
-                    const bool ch0_res = bbox_test(ro, inv, h.t, ch0_min, ch0_max, ch0_dist);
-                    const bool ch1_res = bbox_test(ro, inv, h.t, ch1_min, ch1_max, ch1_dist);
-                    if (!ch0_res && !ch1_res) {
-                        pop();
-                    } else if (ch0_res && ch1_res) {
-                        const bool swap = ch1_dist < ch0_dist;
-                        st.write_at(size++, tos);
-                        tos = swap ? left_child : right_child;
-                        cur = swap ? right_child : left_child;
-                    } else {
-                        cur = ch0_res ? left_child : right_child;
-                    }
+                if ((cur & BVH2_PRIM_COUNT_BITS) == 0) { // TLAS node (reference BVH2)
+                    top_level_node_step(sc.nodes, ro, safe_invert(rd), h.t, st, cur, tos, size);
                 } else { // TLAS leaf: one mesh instance
                     const uint32_t mi = (cur & BVH2_PRIM_INDEX_BITS);
                     const rayhip_mesh_instance &inst = sc.mesh_instances[mi];

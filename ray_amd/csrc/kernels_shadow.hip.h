@@ -28,9 +28,7 @@ __global__ void __launch_bounds__(WAVE, MINW) k_trace_shadow(const SceneView sc,
         TravCount tc = {0, 0, 0, 0, 0};
         f3 rc;
         const uint32_t layer = xy_layer(r.xy, layers);
-        TraceParams tpl = tp;
-        tpl.iteration = tp.iteration + int(layer);
-        tpl.rand_seed = layer == 0 ? tp.rand_seed : layer_rand_seed(tpl.iteration);
+        const TraceParams tpl = layer_params(tp, layer);
         ShadowRay rl = r;
         rl.xy = xy_real(r.xy, layers, layer);
         rc = intersect_scene_shadow<WIDE>(sc, tpl, rl, st, COUNT ? &tc : nullptr);
@@ -196,15 +194,9 @@ __global__ void __launch_bounds__(WAVE, RT_SHADOW_REFILL_MIN_WAVES) k_trace_shad
                 }
                 bool again = false;
                 if (!solid && !over && h.v >= 0.0f) { // the segment ended on a surface that lets light through (rare)
-                    if (h.prim_index < 0) { // (tail of traverse_any: the index indirection)
-                        h.prim_index = -int(sc.tri_indices[-h.prim_index - 1]) - 1;
-                    } else {
-                        h.prim_index = int(sc.tri_indices[h.prim_index]);
-                    }
+                    h.prim_index = resolve_prim_index(sc, h.prim_index); // (tail of traverse_any)
                     const uint32_t layer = xy_layer(xy_virtual, layers);
-                    TraceParams tpl = tp;
-                    tpl.iteration = tp.iteration + int(layer);
-                    tpl.rand_seed = layer == 0 ? tp.rand_seed : layer_rand_seed(tpl.iteration);
+                    const TraceParams tpl = layer_params(tp, layer);
                     const uint32_t rand_hash = hash_combine(hash(xy_real(xy_virtual, layers, layer)), tpl.rand_seed);
                     const uint32_t rand_dim = RAND_DIM_BASE_COUNT + (get_total_depth(depth_word) + crossed) * RAND_DIM_BOUNCE_COUNT;
                     rc *= shadow_surface_throughput(sc, tpl, h, rand_dim, rand_hash);
@@ -280,26 +272,8 @@ __global__ void __launch_bounds__(WAVE, RT_SHADOW_REFILL_MIN_WAVES) k_trace_shad
                 break;
             }
             if (in_c) {
-                if ((cur & BVH2_PRIM_COUNT_BITS) == 0) { // reference BVH2 node: near child first, far child pushed (bvh2_node_step)
-                    const f3 inv = safe_invert(rd);
-                    const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + cur);
-                    const float4 d0 = np[0], d1 = np[1], d2 = np[2], links = np[3];
-                    const uint32_t left_child = float_as_uint(links.x), right_child = float_as_uint(links.y);
-                    const float ch0_min[3] = {d0.x, d0.z, d2.x}, ch0_max[3] = {d0.y, d0.w, d2.y};
-                    const float ch1_min[3] = {d1.x, d1.z, d2.z}, ch1_max[3] = {d1.y, d1.w, d2.w};
-                    float ch0_dist, ch1_dist;
-                    const bool ch0_res = bbox_test(ro, inv, h.t, ch0_min, ch0_max, ch0_dist);
-                    const bool ch1_res = bbox_test(ro, inv, h.t, ch1_min, ch1_max, ch1_dist);
-                    if (!ch0_res && !ch1_res) {
-                        pop();
-                    } else if (ch0_res && ch1_res) {
-                        const bool swap = ch1_dist < ch0_dist;
-                        st.write_at(size++, tos);
-                        tos = swap ? left_child : right_child;
-                        cur = swap ? right_child : left_child;
-                    } else {
-                        cur = ch0_res ? left_child : right_child;
-                    }
+                if ((cur & BVH2_PRIM_COUNT_BITS) == 0) { // reference BVH2 node
+                    top_level_node_step(sc.nodes, ro, safe_invert(rd), h.t, st, cur, tos, size);
                 } else { // one mesh instance
                     const uint32_t mi = (cur & BVH2_PRIM_INDEX_BITS);
                     const rayhip_mesh_instance &inst = sc.mesh_instances[mi];

@@ -8,8 +8,12 @@ Unbundles the gfx950 code object from each object file (section .hip_fatbin, cla
   * where functions only moved -- kernels are emitted in the order the host code first names them -- every symbol's size and bytes instead
     (of a kernel descriptor all but bytes 16..23, the offset to its kernel's code, which is checked to point at that kernel), and the per-kernel
     entries of the metadata note (arguments, registers, LDS, scratch, spills);
-  * the symbol lists.
+  * the symbol lists;
+  * for every kernel whose bytes differ, its size in both builds and the difference of its mnemonic counts (llvm-objdump -d
+    --disassemble-symbols=<kernel>, the first field of each instruction line), or "none": a kernel that only took other registers or
+    another operand order holds the same multiset of instructions.
 Exit status 0 when no kernel differs.  Needs no GPU."""
+import collections
 import hashlib
 import os
 import re
@@ -83,9 +87,32 @@ class CodeObject:
         return self.raw[off + addr - saddr:off + addr - saddr + size]
 
 
+def mnemonic_counts(co, kernel):
+    """the multiset of instruction mnemonics of one kernel: the first field of every instruction line of its disassembly"""
+    counts = collections.Counter()
+    for line in sh(llvm("llvm-objdump"), "-d", f"--disassemble-symbols={kernel}", co).splitlines():
+        if line.startswith(("\t", " ")) and line.split():
+            counts[line.split()[0]] += 1
+    return counts
+
+
+def note_differences(x, y):
+    """the scalar fields of two per-kernel note entries that differ, as 'field a -> b'"""
+    x, y = x or {}, y or {}
+    out = []
+    for f in sorted(set(x) | set(y)):
+        if x.get(f) != y.get(f):
+            is_list = isinstance(x.get(f, y.get(f)), list)  # (.args and the like: named, not printed)
+            out.append(f"{f} (list field)" if is_list else f"{f} {x.get(f)} -> {y.get(f)}")
+    return out
+
+
 def main(obj_a, obj_b):
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        a, b = CodeObject(obj_a, ta), CodeObject(obj_b, tb)
+        return compare(CodeObject(obj_a, ta), CodeObject(obj_b, tb))
+
+
+def compare(a, b):
     for sec in (".text", ".rodata", ".note"):
         x, y = a.section(sec), b.section(sec)
         print(f"{sec}: {'identical' if x == y else 'differs'} ({len(x)} / {len(y)} bytes, sha256 {hashlib.sha256(x).hexdigest()[:16]} / {hashlib.sha256(y).hexdigest()[:16]})")
@@ -110,11 +137,18 @@ def main(obj_a, obj_b):
             differ.append(s)
     kernels = sum(1 for s in common if a.symbols[s][2] == "FUNC")
     print(f"common symbols: {len(common)}, {kernels} of them functions; at another address: {moved}; size or bytes differ: {differ}")
+    # every kernel whose bytes differ: its size in both builds, and what the two builds' multisets of mnemonics do not share
+    for s in sorted({d.split(" ")[0] for d in differ}):
+        if a.symbols[s][2] != "FUNC":
+            continue
+        ca, cb = mnemonic_counts(a.path, s), mnemonic_counts(b.path, s)
+        delta = ", ".join(f"{m} {cb[m] - ca[m]:+d}" for m in sorted(set(ca) | set(cb)) if ca[m] != cb[m])
+        print(f"  {s}: {a.symbols[s][1]} / {b.symbols[s][1]} bytes; mnemonic counts: {delta or 'none'}")
     notes_equal = a.notes == b.notes
     print(f"kernels in the metadata note: {len(a.notes)} / {len(b.notes)}; per-kernel entries equal: {notes_equal}")
     for k in sorted(set(a.notes) | set(b.notes)):
         if a.notes.get(k) != b.notes.get(k):
-            print("  differs:", k)
+            print("  differs:", k, "--", "; ".join(note_differences(a.notes.get(k), b.notes.get(k))))
     return 0 if not differ and not only_a and not only_b and notes_equal else 1
 
 
